@@ -12,7 +12,10 @@ already exist (RANK / LOCAL_RANK / WORLD_SIZE in the environment); invoked direc
 `python bench.py --gpus N` this process only LAUNCHES the N ranks as children (before anything touches
 the GPU -- it never initialises HIP itself and never exec()s) and relays rank 0's JSON line.
 
-Rank 0 prints ONE JSON line.  `roofline` is for the dominant kernel (the fused set-abstraction MLP
+Rank 0 prints ONE JSON line.  A plain run sets up, warms up, times the --steps steps, writes the last timed step's predictions
+when --dump-outputs DIR is given, and prints the headline keys (metric, value, unit, ms_per_step, dtype, config, ...).  Everything
+else -- the kernel rooflines and HBM traffic, the other arithmetic modes, latency, host-buffer, sustained and CPU-baseline legs, the
+multi-GPU self-checks -- runs only with --full.  With --full, `roofline` is for the dominant kernel (the fused set-abstraction MLP
 128-196-256, launch site enc.sa2 branch 1), timed with HIP events inside the timed region:
 `achieved`/`frac` count the ALGORITHMIC fp32 multiply-adds against the peak of the matrix pipe the
 mode runs on, `executed`/`executed_frac` the plane products the split arithmetic really issues.
@@ -54,6 +57,8 @@ DTYPE = {"f32": "f32 (v_mfma_f32_32x32x2_f32)",
 # (16384 rows x (128*196 + 196*256) MAC; layer 1 is not in this kernel) -- DESIGN.md "Measurement"
 PROFILED_TAG = "sa2.1"
 PROFILED_MAC_PER_WINDOW = 128 * 128 * (128 * 196 + 196 * 256)
+DUMP_LIMIT_BYTES = 60 << 20        # --dump-outputs: the arrays of all files together (headers aside, under 64 MB)
+DUMP_SAMPLE_SEED = 0               # --dump-outputs: which windows are kept when the outputs exceed the limit
 
 
 def launch_sites(N):
@@ -119,7 +124,20 @@ def parse(argv=None):
     ap.add_argument("--stub", action="store_true",
                     help="CPU self-test of the multi-rank plumbing (launcher, gloo all-gather, max-over-ranks timing) with fabricated "
                          "predictions; prints a line marked \"stub\": true that is not a measurement")
-    return ap.parse_args(argv)
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check everything beyond the headline figure: kernel rooflines, HBM traffic, the other arithmetic "
+                         "modes, latency, host-buffer, sustained and CPU-baseline legs, the multi-GPU self-checks (each --no-* switch above "
+                         "still drops its part).  Without it a run sets up, warms up, times --steps steps, writes --dump-outputs and prints "
+                         "the headline line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the predictions of the LAST timed step (rank 0: the global batch) as DIR/<name>.npy, "
+                         "float32 (float64 where the output is float64 or an integer), at most %d MiB in all: a larger output is cut to the "
+                         "same seeded sample of windows in every file" % (DUMP_LIMIT_BYTES >> 20))
+    a = ap.parse_args(argv)
+    if not a.full:
+        a.no_host_io = a.no_legs = a.no_latency = a.no_cpu_baseline = a.no_selfcheck = True
+        a.no_sustained = a.no_second_site = a.no_traffic = True
+    return a
 
 
 # ------------------------------------------------------------------------------------------------ launcher
@@ -341,9 +359,11 @@ def expected_line_keys(world, a):
     """The keys rank 0's line of a REAL (non-stub) run carries at this world size and with these switches -- one definition, used by
     run_rank to check its own line (`line_complete`), by the CPU launcher tests (stub lines list it as `would_emit`: world 2 and 8)
     and by tests/test_gpu_bench.py on the forced 1-rank RCCL path.  A multi-GPU line is graded like the 1-GPU one: it carries
-    `roofline` (traffic from the committed PMC profile, marked as such) and `cpu_baseline` too."""
-    keys = ["metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling", "vs_baseline", "dtype", "data", "config",
-            "ms_per_step_per_rank", "roofline", "hbm", "line_complete"]
+    `roofline` (traffic from the committed PMC profile, marked as such) and `cpu_baseline` too.  Without --full: the headline keys only."""
+    keys = ["metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling", "vs_baseline", "dtype", "data", "config"]
+    if not a.full:
+        return sorted(keys)
+    keys += ["ms_per_step_per_rank", "roofline", "hbm", "line_complete"]
     if not a.no_cpu_baseline:
         keys.append("cpu_baseline")
     if not a.no_sustained:
@@ -446,6 +466,50 @@ def stub_outputs(B, N, rank):
     return out
 
 
+def output_arrays(out, prefix=""):
+    """{name: float32 / float64 numpy array} of the tensors in a prediction dict (nested dicts flattened with `_`: class_logits,
+    left_vertices, ...).  Host-side constants that come with it (the tiled `faces`, numpy) are inputs, not predictions."""
+    import numpy as np
+    import torch
+    arrays = {}
+    for k, v in out.items():
+        if isinstance(v, dict):
+            arrays.update(output_arrays(v, prefix + k + "_"))
+        elif torch.is_tensor(v):
+            t = v.detach().cpu()
+            arrays[prefix + k] = t.numpy().astype(np.float64 if t.dtype == torch.float64 or not t.is_floating_point() else np.float32)
+    return arrays
+
+
+def dump_outputs(directory, out, limit=DUMP_LIMIT_BYTES):
+    """--dump-outputs: write output_arrays(out) as directory/<name>.npy.  Above `limit` bytes in all, every array that has one row per
+    window keeps the same windows (a sorted sample drawn with DUMP_SAMPLE_SEED, as many as fit); the others are cut to a seeded
+    sample of their elements.  Returns {name: shape written}."""
+    import numpy as np
+    arrays = output_arrays(out)
+    total = sum(v.nbytes for v in arrays.values())
+    if total > limit:
+        windows = max((v.shape[0] for v in arrays.values() if v.ndim), default=0)
+        per_window = sum(v.nbytes // v.shape[0] for v in arrays.values() if v.ndim and v.shape[0] == windows)
+        rest = sum(v.nbytes for v in arrays.values() if not (v.ndim and v.shape[0] == windows))
+        keep = max(1, min(windows, (limit - rest) // max(per_window, 1)))
+        rows = np.sort(np.random.default_rng(DUMP_SAMPLE_SEED).choice(windows, size=keep, replace=False))
+        for k, v in list(arrays.items()):
+            if v.ndim and v.shape[0] == windows:
+                arrays[k] = v[rows]
+        total = sum(v.nbytes for v in arrays.values())
+        if total > limit:                   # (one window alone too large: a flat element sample of each array, in proportion)
+            for k, v in list(arrays.items()):
+                n = max(1, v.size * limit // total)
+                if n < v.size:
+                    idx = np.sort(np.random.default_rng(DUMP_SAMPLE_SEED).choice(v.size, size=n, replace=False))
+                    arrays[k] = v.reshape(-1)[idx]
+    os.makedirs(directory, exist_ok=True)
+    for k, v in arrays.items():
+        np.save(os.path.join(directory, k + ".npy"), np.ascontiguousarray(v))
+    return {k: list(v.shape) for k, v in arrays.items()}
+
+
 # ------------------------------------------------------------------------------------------------ one rank
 def run_rank(a) -> int:
     import torch
@@ -526,7 +590,7 @@ def run_rank(a) -> int:
         net.eval()
         xyz = synth.synth_cloud(a.cloud, B, Cc, N, seed=1000 + rank).to(dev)       # per-rank seed == distinct windows
         L = _lib.lib()
-        ev = HipEvents(max(a.steps, 1))
+        ev = HipEvents(max(a.steps, 1)) if a.full else None       # (the roofline's HIP events around one launch per timed step)
 
         closs = dev_faces = None
         if a.collision:
@@ -596,13 +660,15 @@ def run_rank(a) -> int:
 
     def timed(nsteps, hook=None, every=0):
         sync()
+        r = None
         t0 = time.perf_counter()
         for i in range(nsteps):
-            step()
+            r = step()
             if hook is not None and every and i % every == every // 2:
                 hook()
         sync()
         dt_ = time.perf_counter() - t0
+        timed.last = r                       # what the last step returned (a dict, or a ticket / pending gather whose result() is one)
         tmax = torch.tensor([dt_], device=cdev, dtype=torch.float64)
         if use_dist:
             dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
@@ -623,13 +689,16 @@ def run_rank(a) -> int:
         last = step()
     sync()
     site1, site2 = launch_sites(N)
-    if L is not None:
+    if ev is not None:
         L.ev2h_profile_set(site1["tag"].encode(), ev.start, ev.stop, ev.n)
     dt = timed(a.steps)
     local_dt = timed.local                   # this rank's own wall time of the timed region (later timed() calls overwrite timed.local)
-    if L is not None:
+    if ev is not None:
         L.ev2h_profile_set(None, None, None, 0)
     main_kernel_ms = ev.elapsed_ms(a.steps) if ev is not None else []
+    if a.dump_outputs and rank == 0:         # before any other leg runs a step: the last TIMED step's predictions
+        last_out = timed.last if isinstance(timed.last, dict) else timed.last.result()
+        dump_outputs(a.dump_outputs, last_out)
     second_kernel_ms = []
     if L is not None and not a.no_second_site:     # the second-largest launch, bracketed in a short run of its own (outside `value`)
         k2 = max(3, min(a.steps // 4, 20))
@@ -638,7 +707,7 @@ def run_rank(a) -> int:
         timed(k2)
         L.ev2h_profile_set(None, None, None, 0)
         second_kernel_ms = ev2.elapsed_ms(k2)
-    rank_ms = [round(v / a.steps * 1e3, 3) for v in all_ranks(local_dt)]        # every rank's own wall time per step
+    rank_ms = [round(v / a.steps * 1e3, 3) for v in all_ranks(local_dt)] if a.full else None       # every rank's own wall time per step
     # value_sustained: the SAME step over a region of >= 2 s, with the shader clock observed while it runs (one-wave probes on a
     # stream of their own, ev2h_shader_clock_probe).  The matrix-pipe kernels are power-limited on real data (2.39 GHz idle boost ->
     # ~1.65 GHz under load, profiles/r*_mfma_ceiling.txt): the driver's `--steps 20` region lasts a quarter of a second, so a reader
@@ -844,7 +913,12 @@ def run_rank(a) -> int:
             res["would_emit"] = expected_line_keys(world, a)      # what the real path prints at this world size (tests/test_bench_launcher.py)
             res["gathered_rows"] = int(last["class_logits"].shape[0]) if last is not None else None
             res["gathered_rank_ids"] = sorted({int(v) for v in last["class_logits"][:, 0, 0].tolist()}) if last is not None else None
-        else:
+        elif use_dist:
+            try:
+                res["config"]["rccl_version"] = ".".join(str(v) for v in torch.cuda.nccl.version())
+            except Exception:  # noqa: BLE001
+                res["config"]["rccl_version"] = None
+        if a.full and not a.stub:
             live, live_src = None, None
             if world == 1 and not a.no_traffic:
                 try:
@@ -859,11 +933,6 @@ def run_rank(a) -> int:
             res["ms_per_step_per_rank"] = {"min": min(rank_ms), "max": max(rank_ms), "all": rank_ms}
             if selfcheck:
                 res["multi_gpu_selfcheck"] = selfcheck
-            if use_dist:
-                try:
-                    res["config"]["rccl_version"] = ".".join(str(v) for v in torch.cuda.nccl.version())
-                except Exception:  # noqa: BLE001
-                    res["config"]["rccl_version"] = None
             live_is_site1 = bool(live) and ("kernel_launches_sampled" in live or site1["tag"] == PROFILED_TAG)
             res["roofline"] = roofline_entry(a.precision, B, main_kernel_ms, live["kernel"] if live_is_site1 else None,
                                              live_src if live_is_site1 else None, site=site1, n_points=N)

@@ -23,7 +23,7 @@ def _line(stdout):
 
 
 def test_direct_invocation_launches_its_own_ranks():
-    p = subprocess.run([sys.executable, BENCH, "--gpus", "2", "--steps", "3", "--warmup", "1", "--stub", "--batch", "3", "--points", "128"],
+    p = subprocess.run([sys.executable, BENCH, "--gpus", "2", "--steps", "3", "--warmup", "1", "--stub", "--batch", "3", "--points", "128", "--full"],
                        env=_clean_env(), capture_output=True, text=True, timeout=600)
     assert p.returncode == 0, p.stderr[-2000:]
     d = _line(p.stdout)
@@ -40,7 +40,7 @@ def test_direct_invocation_launches_its_own_ranks():
 
 def test_eight_ranks_as_the_driver_will_run_it():
     """World size 8 (the driver's largest run) through the same plumbing: launcher, pipelined all-gather, max-over-ranks timing."""
-    p = subprocess.run([sys.executable, BENCH, "--gpus", "8", "--steps", "4", "--warmup", "2", "--stub", "--batch", "2", "--points", "128"],
+    p = subprocess.run([sys.executable, BENCH, "--gpus", "8", "--steps", "4", "--warmup", "2", "--stub", "--batch", "2", "--points", "128", "--full"],
                        env=_clean_env(), capture_output=True, text=True, timeout=600)
     assert p.returncode == 0, p.stderr[-2000:]
     d = _line(p.stdout)
@@ -53,7 +53,7 @@ def test_eight_ranks_as_the_driver_will_run_it():
 def test_expected_line_keys_follow_the_switches():
     sys.path.insert(0, ROOT)
     import bench
-    a = bench.parse(["--gpus", "8", "--no-cpu-baseline", "--no-sustained"])
+    a = bench.parse(["--gpus", "8", "--full", "--no-cpu-baseline", "--no-sustained"])
     keys = bench.expected_line_keys(8, a)
     assert "cpu_baseline" not in keys and "value_sustained" not in keys and "roofline" in keys and "multi_gpu_selfcheck" in keys
     assert bench.newest_profile("r*_mfma_ceiling.txt") is not None            # roofline.sustained_source names the newest round's file
@@ -112,3 +112,74 @@ def test_a_rank_that_dies_ends_the_run_promptly_and_its_log_is_shown():
     assert "simulated start-up failure" in p.stderr and "rank 1" in p.stderr
     assert not [ln for ln in p.stdout.splitlines() if ln.startswith("{")]              # no result line from a failed run
     assert os.path.exists(os.path.join(ROOT, "gpurun_out", "bench_rank1.log"))
+
+
+HEADLINE_KEYS = {"metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling", "vs_baseline", "dtype",
+                 "data", "config"}
+
+
+def test_plain_run_prints_the_headline_only():
+    """Without --full a run does only what its headline needs: every side leg is off, the real path would print the headline keys
+    and nothing else, and --steps is the number of timed steps the line reports."""
+    sys.path.insert(0, ROOT)
+    import bench
+    p = subprocess.run([sys.executable, BENCH, "--steps", "5", "--warmup", "2", "--stub", "--batch", "2", "--points", "128"],
+                       env=_clean_env(), capture_output=True, text=True, timeout=600)
+    assert p.returncode == 0, p.stderr[-2000:]
+    d = _line(p.stdout)
+    assert set(d["would_emit"]) == HEADLINE_KEYS
+    assert set(d) - HEADLINE_KEYS == {"stub", "would_emit", "gathered_rows", "gathered_rank_ids"}
+    assert d["steps"] == 5 and d["warmup"] == 2 and d["ms_per_step"] > 0
+    switches = ("no_host_io", "no_legs", "no_latency", "no_cpu_baseline", "no_selfcheck", "no_sustained", "no_second_site", "no_traffic")
+    a = bench.parse(["--steps", "7"])
+    assert not a.full and a.steps == 7 and all(getattr(a, s) for s in switches)
+    a = bench.parse(["--full"])
+    assert a.full and not any(getattr(a, s) for s in switches)
+    assert set(bench.expected_line_keys(1, bench.parse([]))) == HEADLINE_KEYS
+
+
+def test_dump_outputs_of_the_last_timed_step_of_the_global_batch(tmp_path):
+    """--dump-outputs DIR: rank 0 writes the gathered predictions of the last timed step, one float32 .npy per output (the stub's
+    predictions hold the id of the rank that computed the window)."""
+    import numpy as np
+    out = tmp_path / "dump"
+    p = subprocess.run([sys.executable, BENCH, "--gpus", "2", "--steps", "3", "--warmup", "1", "--stub", "--batch", "2", "--points", "128",
+                        "--dump-outputs", str(out)], env=_clean_env(), capture_output=True, text=True, timeout=600)
+    assert p.returncode == 0, p.stderr[-2000:]
+    _line(p.stdout)
+    names = {f[:-4] for f in os.listdir(out)}
+    assert names == {"class_logits"} | {f"{s}_{k}" for s in ("left", "right")
+                                         for k in ("global_orient", "hand_pose", "betas", "transl", "vertices", "j3d")}
+    logits = np.load(out / "class_logits.npy")
+    assert logits.dtype == np.float32 and logits.shape == (4, 4, 128)
+    assert logits[:2].max() == 0.0 and logits[2:].min() == 1.0 and logits[2:].max() == 1.0
+    v = np.load(out / "right_vertices.npy")
+    assert v.dtype == np.float32 and v.shape[0] == 4 and v.shape[2] == 3
+
+
+def test_dump_outputs_keeps_a_fixed_sample_of_windows_within_the_limit(tmp_path):
+    """outputs larger than the limit are cut to one seeded sample of windows, the same in every file and in every run; float64 and
+    integer outputs are written as float64, host-side constants (the tiled faces) not at all."""
+    import numpy as np
+    import torch
+    sys.path.insert(0, ROOT)
+    import bench
+    W = 64
+    out = {"class_logits": torch.arange(W * 4 * 8, dtype=torch.float32).reshape(W, 4, 8),
+           "left": {"vertices": torch.arange(W * 10 * 3, dtype=torch.float64).reshape(W, 10, 3), "faces": np.zeros((W, 5, 3), np.int64)},
+           "window_id": torch.arange(W)}
+    per_window = 4 * 8 * 4 + 10 * 3 * 8 + 8
+    shapes = bench.dump_outputs(str(tmp_path / "a"), out, limit=20 * per_window)
+    assert shapes == bench.dump_outputs(str(tmp_path / "b"), out, limit=20 * per_window)
+    assert sorted(os.listdir(tmp_path / "a")) == ["class_logits.npy", "left_vertices.npy", "window_id.npy"]
+    arrs = {k: np.load(tmp_path / "a" / (k + ".npy")) for k in shapes}
+    assert sum(v.nbytes for v in arrs.values()) <= 20 * per_window and arrs["window_id"].shape == (20,)
+    assert arrs["class_logits"].dtype == np.float32 and arrs["left_vertices"].dtype == np.float64 and arrs["window_id"].dtype == np.float64
+    ids = arrs["window_id"].astype(np.int64)
+    assert len(set(ids.tolist())) == 20 and (np.diff(ids) > 0).all()
+    assert (arrs["class_logits"] == out["class_logits"].numpy()[ids]).all() and (arrs["left_vertices"] == out["left"]["vertices"].numpy()[ids]).all()
+    for k in shapes:
+        assert (np.load(tmp_path / "b" / (k + ".npy")) == arrs[k]).all()
+    # within the limit: everything, unsampled
+    full = bench.dump_outputs(str(tmp_path / "c"), out)
+    assert full["class_logits"] == [W, 4, 8] and full["window_id"] == [W]

@@ -15,7 +15,7 @@ pytestmark = pytest.mark.gpu
 
 def _run(*extra, traffic=False):
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0")
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "12", "--warmup", "2", "--batch", "16", "--no-legs", "--no-latency",
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--steps", "12", "--warmup", "2", "--batch", "16", "--no-legs", "--no-latency",
            "--no-cpu-baseline", *([] if traffic else ["--no-traffic"]), *extra]
     r = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-2000:]
@@ -110,7 +110,7 @@ def test_bench_live_traffic_at_n8192_names_the_query_convolution(precision):
 def test_bench_line_carries_the_cpu_baseline_on_the_multi_gpu_path():
     """the forced 1-rank RCCL path WITH the CPU leg (bounded to a few seconds): the key a SCALE line was missing"""
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0", EV2H_BENCH_FORCE_DIST="1")
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "6", "--warmup", "1", "--batch", "8", "--no-legs", "--no-latency", "--no-traffic",
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--steps", "6", "--warmup", "1", "--batch", "8", "--no-legs", "--no-latency", "--no-traffic",
            "--no-host-io", "--no-second-site", "--no-selfcheck", "--sustained-seconds", "0.3", "--cpu-seconds", "3"]
     r = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-2000:]
@@ -125,7 +125,7 @@ def test_multi_rank_rehearsal_on_one_gpu_prints_a_complete_line(world, inflight)
     first real N-GPU run will execute except RCCL's transport: sharding of the global FPS starts, barriers, max-over-ranks timing,
     per-rank step times / shader clocks / side-stream probes, the CPU leg on rank 0 after the last barrier, the key set."""
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0")
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", str(world), "--shared-device", "--steps", "5", "--warmup", "1", "--batch", "8",
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--gpus", str(world), "--shared-device", "--steps", "5", "--warmup", "1", "--batch", "8",
            "--inflight", str(inflight), "--no-legs", "--no-latency", "--no-traffic", "--no-host-io", "--no-second-site", "--sustained-seconds", "0.3",
            "--cpu-seconds", "2"]
     r = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=1500)
@@ -144,3 +144,53 @@ def test_multi_rank_rehearsal_on_one_gpu_prints_a_complete_line(world, inflight)
     assert j["cpu_baseline"]["value"] > 0
     # 8 windows per rank: no committed PMC profile of THAT workload -- the line must say so instead of quoting the 256-window step's bytes
     assert j["roofline"]["traffic"] is None and j["roofline"]["traffic_kind"] is None and j["hbm"]["bytes_per_step"] is None
+
+
+def test_plain_run_times_its_steps_and_dumps_the_last_one(tmp_path):
+    """The plain run (no --full): the headline keys only, value = windows of the --steps timed steps / their time, and --dump-outputs
+    holds the predictions of the timed path -- those of a forward of the same inputs in this process, and the same in a second run."""
+    import numpy as np
+    import torch
+    sys.path.insert(0, ROOT)
+    from ev2hands_amd import synth
+    from ev2hands_amd.model import TEHNetWrapper
+
+    def plain(d):
+        cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "7", "--warmup", "2", "--batch", "16", "--dump-outputs", str(d)]
+        r = subprocess.run(cmd, cwd=ROOT, env=dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0"), capture_output=True, text=True, timeout=600)
+        assert r.returncode == 0, r.stderr[-2000:]
+        lines = [ln for ln in r.stdout.strip().splitlines() if ln.startswith("{")]
+        assert len(lines) == 1 and r.stdout.strip().splitlines()[-1] == lines[0], r.stdout[-2000:]
+        return json.loads(lines[0])
+
+    j = plain(tmp_path / "a")
+    assert set(j) == {"metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling", "vs_baseline",
+                      "dtype", "data", "config"}, sorted(j)
+    assert j["steps"] == 7 and j["warmup"] == 2 and j["metric"] == "event-windows/sec at B=16 N=2048 (f16x2)"
+    assert abs(j["value"] - 16 * 1e3 / j["ms_per_step"]) <= 0.01 * j["value"]
+    plain(tmp_path / "b")
+    names = sorted(f[:-4] for f in os.listdir(tmp_path / "a"))
+    assert names == sorted(f[:-4] for f in os.listdir(tmp_path / "b")) and "class_logits" in names and "right_vertices" in names
+    got = {k: np.load(tmp_path / "a" / (k + ".npy")) for k in names}
+    for k in names:
+        assert got[k].dtype == np.float32 and np.isfinite(got[k]).all(), k
+        assert (np.load(tmp_path / "b" / (k + ".npy")) == got[k]).all(), k
+    assert got["class_logits"].shape == (16, 4, 2048)
+
+    # the same inputs as bench.py's rank 0 builds them, through the same wrapper
+    os.environ["ERPC"] = "0"
+    assets = {s: synth.synth_mano_assets(s, 0) for s in ("left", "right")}
+    net = TEHNetWrapper("cuda:0", mano_assets=assets, precision="f16x2")
+    net.load_state_dict(synth.synth_state_dict(4, 0), strict=True)
+    net.eval()
+    net.net.fps_init = synth.fps_inits(16, 2048, 7)
+    with torch.no_grad():
+        out = net.net(synth.synth_cloud("E", 16, 4, 2048, seed=1000).cuda(), net.hands)
+    torch.cuda.synchronize()
+    ref = {"class_logits": out["class_logits"]}
+    for side in ("left", "right"):
+        ref.update({f"{side}_{k}": v for k, v in out[side].items() if torch.is_tensor(v)})
+    assert sorted(ref) == names
+    for k in names:
+        r = ref[k].float().cpu().numpy()
+        assert float(np.abs(got[k] - r).max()) <= 1e-6 * max(float(np.abs(r).max()), 1e-30), k
