@@ -603,7 +603,8 @@ struct GOCfg {
 // of 2..8 workgroups (one window at a time: every M = 128 B layer) has nobody to hide it, and its time is (K / 32) x that chain.
 // Same tiles, same MFMA order: bit-identical to the single-buffer kernel, so the choice (by launch size) never shows in a result.
 // ZS (TAP3 only): the epilogue forms the attention's key-weighted sums instead of storing the tile (zsum_epilogue) -- its own
-// instantiation, not a run-time choice inside one body (see sab_split_forms in sa_mlp_bf16.hip for what one body with two forms costs)
+// instantiation, not a run-time choice inside one body (see the MODE 0 / MODE 3 split in sa_mlp_bf16.hip for what one body with two
+// forms costs)
 template <int NS, bool TAP3, bool PIPE = false, bool ZS = false>
 __global__ __launch_bounds__(GO_THREADS, 3) void gemm_nt_bf16_occ_kernel(GemmBP p, const char* __restrict__ Ws) {
     static_assert(!ZS || TAP3, "the q1-free epilogue belongs to the tap kernel");
@@ -836,11 +837,6 @@ __global__ __launch_bounds__(GO_THREADS, 3) void gemm_nt_bf16_occ_kernel(GemmBP 
         zsum_epilogue<NS>(p, acc, m0, wm, wn, n0, smem, tid);
         return;
     }
-#ifdef EV2H_GEMM_ONE_BODY            // build A/B: both epilogues in the tap kernel's one body, chosen at run time (the form until round 5)
-    if constexpr (TAP3) {
-        if (p.zs_out) { zsum_epilogue<NS>(p, acc, m0, wm, wn, n0, smem, tid); return; }
-    }
-#endif
     gemm_epilogue<NS, 2, 2, false>(p, acc, m0, wm * 64, n0 + wn * 64, wm, wn * 64, GO_BN, reinterpret_cast<float*>(smem), tid);
 }
 
@@ -1031,15 +1027,10 @@ int ev2h_gemm_bf16_zsum(const ev2h_gemm_desc* d, const float* key_pm, float* zpa
     if (x_bf16 && d->precision == EV2H_PREC_F16) { p.x_scale = x_scale; p.x_amax = p.x_amax2 = nullptr; p.x_group_rows = d->x_group_rows; }
     p.tiles_n = d->N / GO_BN;
     p.nblk = (d->M / GB_BM) * p.tiles_n;
-#ifdef EV2H_GEMM_ONE_BODY
-    constexpr bool ZS = false;
-#else
-    constexpr bool ZS = true;
-#endif
-    if (d->precision == EV2H_PREC_F16X2) return launch_go_t<2, true, ZS>(p, (const char*)d->Ws, (hipStream_t)stream);
-    if (d->precision == EV2H_PREC_BF16) return launch_go_t<1, true, ZS>(p, (const char*)d->Ws, (hipStream_t)stream);
-    if (d->precision == EV2H_PREC_BF16X3) return launch_go_t<3, true, ZS>(p, (const char*)d->Ws, (hipStream_t)stream);
-    if (d->precision == EV2H_PREC_F16) return launch_go_t<4, true, ZS>(p, (const char*)d->Ws, (hipStream_t)stream);
+    if (d->precision == EV2H_PREC_F16X2) return launch_go_t<2, true, true>(p, (const char*)d->Ws, (hipStream_t)stream);
+    if (d->precision == EV2H_PREC_BF16) return launch_go_t<1, true, true>(p, (const char*)d->Ws, (hipStream_t)stream);
+    if (d->precision == EV2H_PREC_BF16X3) return launch_go_t<3, true, true>(p, (const char*)d->Ws, (hipStream_t)stream);
+    if (d->precision == EV2H_PREC_F16) return launch_go_t<4, true, true>(p, (const char*)d->Ws, (hipStream_t)stream);
     return EV2H_ERR_ARG;
 }
 

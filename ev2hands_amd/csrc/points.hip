@@ -82,11 +82,7 @@ __global__ __launch_bounds__(THREADS) void fps_kernel(const float4* __restrict__
     // REG_PTS: a thread keeps its points' coordinates in registers.  Not at 32 points per thread in the 1024-thread form (N > 16 384):
     // 4 x 32 values do not fit the 128 registers of a 16-wave workgroup (the instantiation spilled 208 bytes into the serial loop) --
     // there only the running minima stay in registers and the coordinates are read again every step (coalesced, L2-resident).
-#ifdef EV2H_FPS_REG_PTS_ALL      // (build switch for the A/B: the old form, spilling)
-    constexpr bool REG_PTS = true;
-#else
     constexpr bool REG_PTS = !(PPT >= 32 && THREADS >= 1024);
-#endif
     float px[REG_PTS ? PPT : 1], py[REG_PTS ? PPT : 1], pz[REG_PTS ? PPT : 1], md[PPT];
 #pragma unroll
     for (int j = 0; j < PPT; ++j) {

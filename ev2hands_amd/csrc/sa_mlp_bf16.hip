@@ -101,13 +101,6 @@ __device__ long long g_sab_timeline[256];
 // one body that chooses at run time keeps both forms' registers live (128-196-256: 249 registers instead of 224 / 214 in F16X2, a
 // 92-byte spill in BF16X3; the BF16 feature-row kernels 158 -> 124, which doubles the resident workgroups per CU) and schedules around
 // the branch.  Same-box: F16X2 step +2.3 %, BF16 +4 % (profiles/r5_ab_split_forms.txt).
-// EV2H_BUILD_DEFS=-DEV2H_NO_SPLIT_FORMS: BF16 and F16X2 as one body again (A/B; BF16X3 has no such build -- it would spill).
-#ifdef EV2H_NO_SPLIT_FORMS
-constexpr bool SAB_SPLIT12 = false;
-#else
-constexpr bool SAB_SPLIT12 = true;
-#endif
-template <int NS> constexpr bool sab_split_forms() { return NS == 3 || SAB_SPLIT12; }
 constexpr int SAB_WAVES = 8;
 constexpr int SAB_THREADS = SAB_WAVES * 64;
 
@@ -134,12 +127,7 @@ struct SaBCfg {
     // [r6] the L1F A rows carry a 16-byte pad (80 / 112 instead of 64 / 96 bytes): at 64 bytes per row the 32 rows a fragment read
     // touches fall on 4 of the LDS's 256-byte bank windows eight deep -- SQ_LDS_BANK_CONFLICT 15.6 M cycles per launch in the
     // feature-row form against 0 in the table form (profiles/r5_pmc_sq_f16x2.txt); padded like the weight tiles they are conflict free.
-    // EV2H_BUILD_DEFS=-DEV2H_L1F_NO_PAD: the unpadded rows (A/B).
-#ifdef EV2H_L1F_NO_PAD
-    static constexpr int RSA = (NS == 3) ? 96 : 64;
-#else
     static constexpr int RSA = (NS == 3) ? 112 : 80;
-#endif
     static constexpr int W1B = (NS == 1 || NS == 4) ? C1 * 32 : F16 ? C1 * RSA + SAB_WAVES * C1 * 4 : C1 * RSA + C1 * 4;
     // range-record combine (F16X2, end of a group): 8 x (window, max) in the streamed variants, REC_SLOTS per-window running maxima
     // in the resident one -- see the kernel's epilogue
@@ -164,11 +152,7 @@ struct SaBCfg {
     //  * layer 3, last 16-slot k-block (4 live slots): the slots carry [xh | xl | xh | 0] against [wh | wh | wl | 0] -- ONE MFMA
     //    instead of three.
     // 24 of the 480 MFMAs of a 128-196-256 strip (5 %) disappear; the products are the same three (plus wl*xl in layer 2).
-#ifdef EV2H_NO_PACK4
-    static constexpr bool PACK4 = false;
-#else
     static constexpr bool PACK4 = (NS == 2) && REM >= 1 && REM <= 4;
-#endif
 };
 
 // RES = false: weight tiles are streamed, two LDS buffers, one barrier per tile (any MLP width).
@@ -182,22 +166,15 @@ struct SaBCfg {
 // Waves per SIMD the register allocator must leave room for: 2 (256 registers) everywhere, except F16's resident feature-row kernels
 // whose LDS footprint lets TWO workgroups share a CU -- BF16's get under 128 registers by themselves (124), F16's 64-96-128 needs 138
 // and is held to 128 (32 bytes of scratch outside the MFMA loops): kbench 0.81 -> 0.73 ms (tools/kbench.py sab, KBENCH_FEAT=1).
-// EV2H_BUILD_DEFS=-DEV2H_F16_RES_ONE_WG: build without (A/B).
 template <int C1, int C2, int C3, int NS, bool RES, int MODE>
 constexpr int sab_min_waves() {
-#ifdef EV2H_F16_RES_ONE_WG
-    return 2;
-#else
     return (NS == 4 && RES && MODE == 3 && 2 * SaBCfg<C1, C2, C3, NS>::RES_LDS_BYTES <= 160 * 1024) ? 4 : 2;
-#endif
 }
 template <int C1, int C2, int C3, int NS, bool RES, int MODE = 0>
 __global__ __launch_bounds__(SAB_THREADS, (sab_min_waves<C1, C2, C3, NS, RES, MODE>())) void sa_mlp_max_bf16_kernel(SaBP p) {
     constexpr int WV = SAB_WAVES;
-    // MODE = 3: the set abstraction with RAW FEATURE ROWS compiled in (L1M / L1F below; MODE 0 is then the table form only) -- see
-    //              sab_split_forms above.
+    // MODE = 3: the set abstraction with RAW FEATURE ROWS (L1M / L1F below); MODE 0 is the table form only (see above).
     constexpr bool ROWS = MODE == 1 || MODE == 2, DIRECT = MODE == 2;
-    static_assert(MODE != 3 || sab_split_forms<NS>(), "MODE 3 is the feature-row form of the modes that compile it separately");
     static_assert(!(RES && ROWS), "the row-output variants stream their tiles");
     // BF16, set abstraction: LAYER 1 ON THE MATRIX PIPE.  D1[channel][neighbour] = A1 [32 channels][16 k] x B1 [16 k][32 neighbours]
     // (+ C = the gathered table row when the features are a table) with the k slots
@@ -225,59 +202,18 @@ __global__ __launch_bounds__(SAB_THREADS, (sab_min_waves<C1, C2, C3, NS, RES, MO
     // BF16X3 with raw feature rows [r5]: the same without any factor.  B1f = [x0(8) | x1(8)], B1g = [x0 | x2] (x = x0 + x1 + x2, the exact
     // three-plane split), A = [w2 | w0] (x B1g), [w1 | w1], [w0 | w0] (x B1f): three MFMAs = the six products of Planes<3>, small terms
     // first, on top of C = b1.
-    constexpr bool L1F = !ROWS && (NS == 2 || NS == 3) && (!sab_split_forms<NS>() || MODE == 3);
+    constexpr bool L1F = (NS == 2 || NS == 3) && MODE == 3;
     // L2PIPE / H2FUSE (round 4, late): conversion work of one wave placed between its MFMA groups (see the layer-2 loop and the first
     // layer-3 step).  Same-box step A/B (profiles/r4_ab_h2fuse_l2pipe.txt): BF16 +1.3 % with H2FUSE, +1.9 % with both; F16X2 +1.1 % with
     // H2FUSE, and L2PIPE costs it 0.5 % (its widest instantiation then spills 24 bytes) -- so F16X2 keeps the un-pipelined layer 2.
-    // EV2H_BUILD_DEFS=-DEV2H_NO_L2PIPE / -DEV2H_NO_H2FUSE: build without.
-#ifdef EV2H_NO_L2PIPE
-    constexpr bool L2PIPE = false;
-#else
-#ifdef EV2H_L2PIPE2
-    constexpr bool L2PIPE = !ROWS && NS <= 2 && (C1 / 32) % 2 == 0;      // build experiment: F16X2 too
-#else
-#ifdef EV2H_F16_NO_L2PIPE
-    constexpr bool L2PIPE = !ROWS && NS == 1 && (C1 / 32) % 2 == 0;
-#else
     constexpr bool L2PIPE = !ROWS && (NS == 1 || NS == 4) && (C1 / 32) % 2 == 0;      // (F16 [r6]: bf16's layer-1 form, bf16's pipelining)
-#endif
-#endif
-#endif
-#ifdef EV2H_NO_H2FUSE
-    constexpr bool H2FUSE = false;
-#else
     constexpr bool H2FUSE = NS != 3;          // (BF16X3: the widest instantiation would spill)
-#endif
     // F16X2 [r5]: with the two layer-1 forms in separate instantiations there are registers for the second fragment set (128-196-256:
     // 224 -> 232): dominant launch 1.622 -> 1.592 ms, step +0.65 % same-box (profiles/r5_ab_frag_pipe_f16x2.txt).  BF16X3 would spill
-    // (28 bytes in the widest instantiation).  EV2H_BUILD_DEFS=-DEV2H_NO_FRAG_PIPE2: F16X2 without (A/B).
-#ifdef EV2H_NO_FRAG_PIPE2
-    constexpr bool FRAG_PIPE = (NS == 1 || NS == 4);
-#else
+    // (28 bytes in the widest instantiation).
     constexpr bool FRAG_PIPE = (NS != 3);
-#endif
     using Cfg = SaBCfg<C1, C2, C3, NS>;
     using PL = Planes<NS>;
-    // L3T16 [r6]: LAYER 3 ON v_mfma_f32_16x16x32 (planes.hpp: mfma16_planes).  A pure stream of that instruction sustains 0.73-0.77 of the
-    // 2.5 PFLOP/s peak on random operands where the 32 x 32 x 16 form sustains 0.62-0.65 (same FLOP per cycle, a quarter of the
-    // accumulator traffic: the power limit sets the clock, profiles/r6_mfma_ceiling.txt), and layer 3 is 62 % of this kernel's MFMA work.
-    // Layers 1-2 keep the 32 x 32 form and its D layout (lane = neighbour j, registers = channels); the A operand of a 16 x 16 x 32 MFMA
-    // wants lane group G = l >> 4 to hold k-group G of neighbour l & 15, which is a regrouping of 16-lane rows between the two k-block
-    // registers of a tile: P = h2p[.][t][0] = rows [P0 P1 P2 P3], Q = h2p[.][t][1]; v_permlane32_swap then v_permlane16_swap (gfx950,
-    // one VALU op each; tools/ubench/permlane_swap_check.hip) give [P0 P2 Q0 Q2] = neighbours 0..15 x k-groups 0..3 and [P1 P3 Q1 Q3]
-    // = neighbours 16..31.  The W3 images are read as they are (16-row fragments: row l & 15, 16 bytes at k offset 32 t + 8 G).
-    // Same products, same plane order; the sums associate differently (32 k per MFMA, two neighbour tiles), so results agree with
-    // the 32 x 32 form to fp32 rounding, not bit for bit (all 100 set-abstraction operator tests pass with it).
-    // MEASURED AND NOT ADOPTED (profiles/r6_ab_l3t16_refuted.txt): the kernels are no faster (kbench: 1.653 / 1.807 / 1.747 ms against
-    // 1.638 / 1.835 / 1.756 for the three 128-196-256 shapes) and the whole step is 1.6 % (f16x2) / 2.0 % (f16) SLOWER, same box,
-    // builds interleaved -- the pure-stream advantage of the smaller tile does not survive the kernel's own mix (112 more VALU ops
-    // per strip for the regrouping, twice the MFMA issue slots).  Opt-in for whoever re-tiles layers 1-2 as well (then the
-    // regrouping disappears): EV2H_BUILD_DEFS=-DEV2H_L3T16.
-#ifdef EV2H_L3T16
-    constexpr bool L3T16 = !ROWS && (NS == 2 || NS == 4) && (RES || Cfg::UPT == 2);
-#else
-    constexpr bool L3T16 = false;
-#endif
     constexpr int NPL = Cfg::NPL;
     constexpr bool F16 = Cfg::F16;
     constexpr int T2 = Cfg::T2, T3 = Cfg::T3, NC1 = Cfg::NC1, RS2 = Cfg::RS2, RS3 = Cfg::RS3, C2P = Cfg::C2P;
@@ -293,9 +229,8 @@ __global__ __launch_bounds__(SAB_THREADS, (sab_min_waves<C1, C2, C3, NS, RES, MO
     const int half = lane >> 5, l31 = lane & 31;
     const int L = xcd_remap(blockIdx.x, p.nblk);
     const int ngroups = p.B * p.S;
-    // hasfeat: the features are raw rows (ev2h_sa_desc.feat) -- a compile-time constant where the two forms are separate instantiations
-    const bool hasfeat = sab_split_forms<NS>() ? (MODE == 3) : (p.feat != nullptr);
-    const bool fmode = L1F && hasfeat;                         // (uniform)
+    constexpr bool hasfeat = MODE == 3;                        // the features are raw rows (ev2h_sa_desc.feat)
+    constexpr bool fmode = L1F && hasfeat;
     // F16X2 feature mode: s1 b1 of this wave's window; BF16X3 feature mode: b1 (one copy)
     float* sb1w = F16 ? reinterpret_cast<float*>(smem + WBYTES + C1 * Cfg::RSA) + wave * C1 : reinterpret_cast<float*>(smem + WBYTES + C1 * Cfg::RSA);
 
@@ -401,9 +336,6 @@ __global__ __launch_bounds__(SAB_THREADS, (sab_min_waves<C1, C2, C3, NS, RES, MO
     // index of this group in the caller's arrays (centroids, index lists, counts, output rows)
     const size_t gf = ROWS ? (size_t)gg : (size_t)b * p.S_total + p.s_off + (gg - b * p.S);
     float mrun[T3];
-    float m16[L3T16 ? T3 : 1][2];          // L3T16: running maxima per 16-channel half of an output tile (this lane's column l & 15)
-#pragma unroll
-    for (int u = 0; u < (L3T16 ? T3 : 1); ++u) m16[u][0] = m16[u][1] = -INFINITY;
 #pragma unroll
     for (int u = 0; u < T3; ++u) mrun[u] = -INFINITY;
 
@@ -421,16 +353,7 @@ __global__ __launch_bounds__(SAB_THREADS, (sab_min_waves<C1, C2, C3, NS, RES, MO
     // few binades of headroom.  The conversion of H2 is then cvt + packed ReLU + packed clamp, without the two multiplies by c2
     // (whole step +6.7 % in a timing build, profiles/r6_f16_chain_scale.txt).  The row chains (ROWS) read rows whose scale
     // their producer chose for the rows alone: they keep the factor.
-#ifdef EV2H_F16_CLAMP
-    constexpr bool F16_CLAMP = true;              // EV2H_BUILD_DEFS=-DEV2H_F16_CLAMP: clamp the fp16 conversions of the F16 mode at 65504 (A/B)
-#else
-    constexpr bool F16_CLAMP = false;
-#endif
-#ifdef EV2H_F16_NO_C2ONE
-    constexpr bool C2ONE = false;                 // EV2H_BUILD_DEFS=-DEV2H_F16_NO_C2ONE: a factor per layer as in f16x2 (A/B)
-#else
     constexpr bool C2ONE = NS == 4 && !ROWS;
-#endif
     float s1 = 1.f, c2 = p.u2, c3 = C2ONE ? p.u3 * p.u2 : p.u3;      // (without range arguments: s1 = 1; C2ONE: H2' = H2 / u2 as accumulated)
     float so = 1.f;                                             // F16 row chain with fp16 output rows: their per-window power of two
     float b1s_f = 1.f, b1s_x = 1.f, b1s_b = 1.f;               // F16 L1M: the B operand's factors s1 a1f, s1 a1x, s1 a1b (wave-uniform)
@@ -508,12 +431,8 @@ __global__ __launch_bounds__(SAB_THREADS, (sab_min_waves<C1, C2, C3, NS, RES, MO
     // table chunk) -- is requested DURING strip s, so that a strip no longer starts with two dependent global-memory latencies
     // (index -> row: 6 of the 28 us of a strip in the phase timeline, with one workgroup per CU and nothing else to run)
     // (F16X2 and BF16: +0.9 % on the f16x2 step, dominant kernel 1.620 -> 1.576 ms, same-box build A/B profiles/r4_ab_xpf.txt;
-    // BF16X3 would spill: its widest instantiation already sits at 256 registers.)  EV2H_BUILD_DEFS=-DEV2H_NO_XPF: build without.
-#ifdef EV2H_NO_XPF
-    constexpr bool XPF = false;
-#else
+    // BF16X3 would spill: its widest instantiation already sits at 256 registers.)
     constexpr bool XPF = !ROWS && NS != 3;
-#endif
     f32x4 raw[4];                 // a lane's 16 gathered layer-1 values of the current chunk (XPF: survives into the next strip)
     int idx_cur = 0, idx_nxt = 0;
     float4 q_cur = make_float4(0.f, 0.f, 0.f, 0.f), f0_cur = q_cur, f1_cur = q_cur;
@@ -747,12 +666,12 @@ __global__ __launch_bounds__(SAB_THREADS, (sab_min_waves<C1, C2, C3, NS, RES, MO
             if constexpr (L1M) {
                 // ReLU on the packed bf16 / fp16 pairs: one v_pk_max_i16 per pair (negative floats are negative int16 patterns in both
                 // formats).  F16: D1 is s1 H1 already (the factors rode on the operands).  No clamp of an overflowed conversion (the
-                // two-plane mode's relu_sat_f16 is free, here it would be a v_pk_min_i16 per pair): see F16_CLAMP
+                // two-plane mode's relu_sat_f16 is free, here it would be a v_pk_min_i16 per pair): see C2ONE
 #pragma unroll
                 for (int w = 2 * j4; w < 2 * j4 + 2; ++w) {
                     unsigned o[1];
                     split_planes<NS>(d1[2 * w], d1[2 * w + 1], o);
-                    bp[w >> 2][0][w & 3] = (F16 && F16_CLAMP) ? sat_pk_f16(relu_pk_bf16(o[0])) : relu_pk_bf16(o[0]);
+                    bp[w >> 2][0][w & 3] = relu_pk_bf16(o[0]);
                 }
             } else if (fmode) {
                 if constexpr (L1F && NS == 3) {
@@ -984,7 +903,7 @@ __global__ __launch_bounds__(SAB_THREADS, (sab_min_waves<C1, C2, C3, NS, RES, MO
                     // contract behind it (dmax) gets inf -> NaN outputs instead of silently clamped ones.  (Same-box A/B, whole step,
                     // profiles/r6_f16_chain_scale.txt: a factor per layer 40 630, chain scale 41 200, without the clamps 41 740 windows/s.)
                     split_planes<NS>(h2[t][2 * k], h2[t][2 * k + 1], o);
-                    o[0] = F16_CLAMP ? sat_pk_f16(relu_pk_bf16(o[0])) : relu_pk_bf16(o[0]);
+                    o[0] = relu_pk_bf16(o[0]);
                 }
                 else if constexpr (F16) split_planes<NS>(relu_sat_f16(h2[t][2 * k] * c2), relu_sat_f16(h2[t][2 * k + 1] * c2), o);
                 else if constexpr (NS == 1) { split_planes<NS>(h2[t][2 * k], h2[t][2 * k + 1], o); o[0] = relu_pk_bf16(o[0]); }     // (u2 = 1: no factor)
@@ -1009,27 +928,14 @@ __global__ __launch_bounds__(SAB_THREADS, (sab_min_waves<C1, C2, C3, NS, RES, MO
         // H2FUSE: only tile 0 is split here; tile t + 1 is split between the MFMA groups of tile t in the FIRST layer-3 step, so that
         // the conversion (VALU) of one wave runs under the MFMAs of its SIMD partner instead of both waves converting while the matrix
         // pipe idles (phase timeline: "h2 ReLU + split" was 8 % of a strip).  Same values, same order of the contraction.
-        // L3T16: regroup the 16-lane rows of tile t's two k-block registers into the A operands of the two neighbour tiles
-        auto perm16 = [&](int t) {
-            if constexpr (L3T16) {
 #pragma unroll
-                for (int s = 0; s < NPL; ++s)
-#pragma unroll
-                    for (int w = 0; w < 4; ++w) {
-                        typedef unsigned u32x2_ __attribute__((ext_vector_type(2)));
-                        const u32x2_ a = __builtin_amdgcn_permlane32_swap(h2p[s][t][0][w], h2p[s][t][1][w], false, false);
-                        const u32x2_ b_ = __builtin_amdgcn_permlane16_swap(a[0], a[1], false, false);
-                        h2p[s][t][0][w] = b_[0];          // neighbours 0..15, k-groups 0..3 of tile t
-                        h2p[s][t][1][w] = b_[1];          // neighbours 16..31
-                    }
-            }
-        };
-#pragma unroll
-        for (int t = 0; t < (H2FUSE ? 1 : T2); ++t) { split_half(t, 0); split_half(t, 1); perm16(t); }
+        for (int t = 0; t < (H2FUSE ? 1 : T2); ++t) { split_half(t, 0); split_half(t, 1); }
         STAMP(39);
 
         // ---------------- layer 3 + max: D3[neighbour][channel] = H2 (A, registers) x W3 tile (B, LDS, permuted k order)
         // set abstraction: the max over the strip's neighbours, kept per output tile
+        // Layer 3 on v_mfma_f32_16x16x32 (with a permlane regrouping of the layer-2 output) was tried in r6 and measured
+        // 1.6-2.0 % slower on the whole step (profiles/r6_ab_l3t16_refuted.txt); the code is in the git history.
         auto finish_tile = [&](int u, const f32x16& acc) {
             float mx = fmaxf(fmaxf(acc[0], acc[1]), acc[2]);
 #pragma unroll
@@ -1057,69 +963,6 @@ __global__ __launch_bounds__(SAB_THREADS, (sab_min_waves<C1, C2, C3, NS, RES, MO
             }
             float b3u = 0.f;
             if constexpr (ROWS) b3u = p.b3[32 * u + l31];      // (requested here, used after the step's MFMAs)
-            if constexpr (L3T16) {
-                // two output tiles (u, u + 1) x two neighbour tiles x two 16-channel halves: eight 16 x 16 accumulators (32 registers,
-                // as the two 32 x 32 ones); groups (t, c): one B fragment per plane and output tile feeds both neighbour tiles
-                f32x4 a16[2][2][2];          // [output tile][neighbour tile][channel half]
-#pragma unroll
-                for (int i = 0; i < 8; ++i) a16[i >> 2][(i >> 1) & 1][i & 1] = f32x4{0.f, 0.f, 0.f, 0.f};
-                const int lg = lane >> 4, l15 = lane & 15;
-                const char* pb16 = cur + l15 * RS3;
-                constexpr int NG16 = 2 * T2;
-                auto ld16 = [&](int g, u32x4 (&x)[2][NPL]) {
-                    const int t = g >> 1, c = g & 1;
-                    // the last tile of a width that fills only its first k-block (M_LAST == 1): k-groups 2, 3 do not exist in the image
-                    // (their A values are exact zeros: padded channels) -- read k-groups 0, 1 again instead of whatever follows the row
-                    const int kg = (t == T2 - 1 && Cfg::M_LAST == 1) ? (lg & 1) : lg;
-#pragma unroll
-                    for (int uu = 0; uu < 2; ++uu)
-#pragma unroll
-                        for (int s = 0; s < NPL; ++s)
-                            x[uu][s] = *reinterpret_cast<const u32x4*>(pb16 + uu * Cfg::TB3 + (16 * c) * RS3 + s * (C2P * 2) + (32 * t + 8 * kg) * 2);
-                };
-                u32x4 fw16[2][2][NPL];
-                if constexpr (FRAG_PIPE) ld16(0, fw16[0]);
-#pragma unroll
-                for (int g = 0; g < NG16; ++g) {
-                    const int t = g >> 1, c = g & 1;
-                    if constexpr (FRAG_PIPE) {
-                        if (g + 1 < NG16) ld16(g + 1, fw16[(g + 1) & 1]);
-                        __builtin_amdgcn_sched_barrier(0);
-                    } else {
-                        ld16(g, fw16[g & 1]);
-                    }
-                    u32x4 (&w)[2][NPL] = fw16[g & 1];
-#pragma unroll
-                    for (int j = 0; j < PL::NPROD; ++j) {
-                        if (Cfg::PACK4 && t == T2 - 1 && !(PL::A[j] == 0 && PL::B[j] == 0)) continue;   // one MFMA holds all three products
-#pragma unroll
-                        for (int uu = 0; uu < 2; ++uu)
-#pragma unroll
-                            for (int nu = 0; nu < 2; ++nu)
-                                a16[uu][nu][c] = mfma16_planes<NS>(h2p[PL::A[j]][t][nu], w[uu][PL::B[j]], a16[uu][nu][c]);
-                    }
-                    if constexpr (FRAG_PIPE) __builtin_amdgcn_sched_barrier(0);
-                    if constexpr (FIRST) {
-                        if (t + 1 < T2) {
-                            if constexpr (!FRAG_PIPE) __builtin_amdgcn_sched_barrier(0);
-                            split_half(t + 1, c);                      // tile t + 1 is converted between the groups of tile t ...
-                            if (c == 1) perm16(t + 1);                 // ... and regrouped once both of its k-blocks exist
-                            __builtin_amdgcn_sched_barrier(0);
-                        }
-                    }
-                }
-                STAMP(41 + 4 * u);
-                // max over this lane's 8 rows (2 neighbour tiles x 4 registers) per (output tile, channel half)
-#pragma unroll
-                for (int uu = 0; uu < 2; ++uu)
-#pragma unroll
-                    for (int c = 0; c < 2; ++c) {
-                        const f32x4 x = a16[uu][0][c], y = a16[uu][1][c];
-                        const float mx = fmaxf(fmaxf(fmaxf(x[0], x[1]), fmaxf(x[2], x[3])), fmaxf(fmaxf(y[0], y[1]), fmaxf(y[2], y[3])));
-#pragma unroll
-                        for (int q = 0; q < T3; ++q) m16[q][c] = (q == u + uu) ? fmaxf(m16[q][c], mx) : m16[q][c];
-                    }
-            } else {
             f32x16 acc, acc1;
 #pragma unroll
             for (int r = 0; r < 16; ++r) { acc[r] = 0.f; acc1[r] = 0.f; }
@@ -1212,7 +1055,6 @@ __global__ __launch_bounds__(SAB_THREADS, (sab_min_waves<C1, C2, C3, NS, RES, MO
                     finish_tile(u, acc);
                 }
             }
-            }       // (!L3T16)
             STAMP(42 + 4 * u);
             if constexpr (!RES) {
                 if ((u + TPS - 1) % UPT == UPT - 1) {
@@ -1228,18 +1070,6 @@ __global__ __launch_bounds__(SAB_THREADS, (sab_min_waves<C1, C2, C3, NS, RES, MO
         for (int u = H2FUSE ? TPS : 0; u < T3; u += TPS) l3_step(u, std::false_type{});
         STAMP(37);
     }
-    if constexpr (L3T16) {
-        // the maxima over the lane groups (rows 4 G + r of both neighbour tiles), then this lane's channel 32 u + (l & 31): its half is
-        // (l >> 4) & 1 -- from here on the epilogue is the 32 x 32 form's (every lane group holds the same reduced values)
-#pragma unroll
-        for (int u = 0; u < T3; ++u) {
-            float v0 = m16[u][0], v1 = m16[u][1];
-            v0 = fmaxf(v0, __shfl_xor(v0, 16, 64)); v1 = fmaxf(v1, __shfl_xor(v1, 16, 64));
-            v0 = fmaxf(v0, __shfl_xor(v0, 32, 64)); v1 = fmaxf(v1, __shfl_xor(v1, 32, 64));
-            mrun[u] = ((lane >> 4) & 1) ? v1 : v0;
-        }
-    }
-
     if constexpr (!ROWS && !RES) {
         if (spg > 1) {
             // combine the strips' partial maxima: [wave][C3] floats in the (now idle) tile buffer; the group's first wave finishes
@@ -1368,7 +1198,7 @@ int launch_sab(SaBP p, hipStream_t st) {
 
 template <int NS, int MODE = 0>
 int dispatch_sab(const SaBP& p, int c1, int c2, int c3, hipStream_t st) {
-    if constexpr (sab_split_forms<NS>() && MODE == 0) {
+    if constexpr (MODE == 0) {
         if (p.feat) return dispatch_sab<NS, 3>(p, c1, c2, c3, st);      // raw feature rows: the feature-row instantiations
     }
     if (c1 == 32 && c2 == 32 && c3 == 64) return launch_sab<32, 32, 64, NS, MODE>(p, st);

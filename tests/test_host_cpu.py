@@ -402,6 +402,19 @@ def test_every_environment_switch_of_the_library_is_listed_in_the_gpu_switch_tes
     assert len(found) <= 8          # keep the A/B surface small
 
 
+def test_the_only_compile_time_switch_of_the_library_is_the_timeline_build():
+    """grep of csrc/: the EV2H_ macros tested by #ifdef / #ifndef / defined() -- the compile-time twin of the test above.  A build
+    A/B switch leaves the source together with its losing arm once its measurement is committed; the phase-timeline build
+    (tools/sa_timeline.py) is instrumentation, not an alternative form."""
+    csrc = os.path.join(ROOT, "ev2hands_amd", "csrc")
+    found = set()
+    for fn in sorted(f for f in os.listdir(csrc) if f.endswith((".hip", ".hpp"))):
+        src = open(os.path.join(csrc, fn)).read()
+        found |= set(re.findall(r"^\s*#\s*if(?:n?def)?\s+(EV2H_[A-Z0-9_]+)\b", src, re.M))
+        found |= set(re.findall(r"\bdefined\s*\(?\s*(EV2H_[A-Z0-9_]+)", src))
+    assert found == {"EV2H_SAB_TIMELINE"}, sorted(found)
+
+
 def test_default_arithmetic_mode_is_auto(monkeypatch):
     """A user who names no mode gets "auto" (f16x2 after a self-check against bf16x3 on the first batch); EV2H_PRECISION and
     precision= still choose explicitly."""

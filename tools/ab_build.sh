@@ -1,6 +1,6 @@
 #!/bin/bash
 # Same-box A/B of two BUILDS of the library (compile-time switches), interleaved:
-#   bash tools/ab_build.sh <rounds> "<EV2H_BUILD_DEFS A>" "<EV2H_BUILD_DEFS B>"      e.g.  bash tools/ab_build.sh 2 "" "-DEV2H_XPF_ALL"
+#   bash tools/ab_build.sh <rounds> "<EV2H_BUILD_DEFS A>" "<EV2H_BUILD_DEFS B>"      e.g.  bash tools/ab_build.sh 2 "" "-DEV2H_MY_SWITCH"
 ROUNDS=${1:-2}; shift
 cd "$GRAFT_REPO_ROOT" 2>/dev/null || cd "$(dirname "$0")/.."
 ARGS=${AB_ARGS:-"--full --steps 100 --warmup 5 --no-legs --no-latency --no-cpu-baseline --no-traffic --no-selfcheck --no-second-site --no-sustained --no-host-io"}
