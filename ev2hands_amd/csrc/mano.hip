@@ -226,7 +226,7 @@ extern "C" int ev2h_mano(const ev2h_mano_consts* c, const float* params, int ldp
     EV2H_CHECK_ARG((verts_stride == 0 || verts_stride >= (size_t)NV * 3) && (joints_stride == 0 || joints_stride >= 63));
     p.c = *c; p.params = params; p.ldp = ldp; p.verts = verts; p.joints = joints;
     p.verts_stride = verts_stride ? verts_stride : (size_t)NV * 3; p.joints_stride = joints_stride ? joints_stride : 63;
-    p.parts = B <= 32 ? 4 : 1;      // a few windows at a time: a hand's vertices over four workgroups (tests: B = 1 .. 64 against the oracle)
+    p.parts = B <= 32 ? 4 : 1;      // a few windows at a time: a hand's vertices over four workgroups (test_gpu_schedules.py::test_mano_across_parts: B = 1 .. 256 against the oracle)
     mano_kernel<<<B * p.parts, MANO_THREADS, 0, (hipStream_t)stream>>>(p);
     EV2H_CHECK_LAUNCH();
     return EV2H_OK;

@@ -1183,7 +1183,7 @@ int launch_sab(SaBP p, hipStream_t st) {
                                            hipFuncAttributeMaxDynamicSharedMemorySize, Cfg::LDS_BYTES)););
     {
         // small grids (a few windows at a time): spread a group's strips over the waves of a workgroup (SaBP::spg).  Chosen by the
-        // launch size only -- the result does not depend on it (a max is exact and order-free; operator tests at 1 .. 64 windows).
+        // launch size only -- the result does not depend on it (a max is exact and order-free; test_gpu_schedules.py::test_sa_window_counts at 1 .. 256 windows).
         const int spg = p.K / 32;
         p.spg = 1;
         if ((spg == 2 || spg == 4) && p.nblk < 256 && SAB_WAVES * C3 * 4 <= 2 * Cfg::TILE) {

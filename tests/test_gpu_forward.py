@@ -129,7 +129,9 @@ def check_against(out, net, ref, trace, B, N, tol=None):
                                               ("E", 4, 8192, 1, 5), ("E", 5, 16384, 1, 9), ("U", 5, 1000, 2, 6), ("E", 4, 128, 1, 7), ("U", 4, 640, 5, 8),
                                               # odd sizes: partial 32-row strips in the row-chain kernels, ragged 256-point partial sums of
                                               # the folded attention, an odd point count, one point past a power of two
-                                              ("E", 4, 333, 3, 9), ("U", 5, 2049, 1, 10), ("E", 4, 130, 2, 11)])
+                                              ("E", 4, 333, 3, 9), ("U", 5, 2049, 1, 10), ("E", 4, 130, 2, 11),
+                                              # 8 windows: enc.sa1's sampling drawn in chunks beside the set abstraction (forward.hip chunk_min_b)
+                                              ("E", 4, 512, 8, 12)])
 def test_forward_matches_oracle(kind, C, N, B, seed, precision):
     """Both fp32-class arithmetic modes must meet the full parity bar (1e-4, argmax and selections exact)."""
     _need_gpu()
@@ -550,7 +552,8 @@ def test_config5_as_eight_shards_of_16_windows_equals_the_128_window_batch(preci
     torch.cuda.empty_cache()
 
 
-@pytest.mark.parametrize("precision,B,N", [("bf16", 256, 2048), ("f16x2", 128, 8192), ("f16x2", 16, 8192), ("bf16", 128, 8192), ("f32", 128, 8192)])
+@pytest.mark.parametrize("precision,B,N", [("bf16", 256, 2048), ("f16", 256, 2048), ("bf16x3", 256, 2048), ("f16x2", 128, 8192), ("f16x2", 16, 8192),
+                                              ("bf16", 128, 8192), ("f32", 128, 8192)])
 def test_baseline_config_sizes_properties(precision, B, N):
     """BASELINE.json config 3 (B=256, N=2048, bf16) and config 5 (N=8192 dense windows, B=128 per GPU) at full size, where the
     CPU oracle would need minutes per window: size-independent properties -- all outputs finite, and reversing the order of the

@@ -402,6 +402,17 @@ def test_every_environment_switch_of_the_library_is_listed_in_the_gpu_switch_tes
     assert len(found) <= 8          # keep the A/B surface small
 
 
+def test_the_schedule_thresholds_the_gpu_schedule_tests_were_sized_for_are_unchanged():
+    """grep of csrc/: the launch-size switches that tests/test_gpu_schedules.py (and one forward case) sweep across.  If one
+    moves, the sweep no longer straddles it: the message names the test to resize."""
+    from test_gpu_schedules import SCHEDULE_THRESHOLDS
+    csrc = os.path.join(ROOT, "ev2hands_amd", "csrc")
+    for fn, text, test in SCHEDULE_THRESHOLDS:
+        src = " ".join(open(os.path.join(csrc, fn)).read().split())
+        assert " ".join(text.split()) in src, (f"csrc/{fn} no longer holds `{text}`: resize {test} so that its sweep straddles the "
+                                               f"new threshold, then update SCHEDULE_THRESHOLDS in tests/test_gpu_schedules.py")
+
+
 def test_the_only_compile_time_switch_of_the_library_is_the_timeline_build():
     """grep of csrc/: the EV2H_ macros tested by #ifdef / #ifndef / defined() -- the compile-time twin of the test above.  A build
     A/B switch leaves the source together with its losing arm once its measurement is committed; the phase-timeline build
