@@ -87,6 +87,8 @@ def pack_f16_families(mask: int) -> int:
     """EV2H_PACK_F16_FAMILIES(mask)"""
     return (int(mask) & 15) << 8
 W_EQUALIZED, W_UNEQUALIZED_OK = 1, 2
+# The demo-frame exports (ev2h_event_window_pixels, ev2h_demo_point_panels, ev2h_render_*) are purely additive -- no struct or existing
+# signature changed -- so the version stays 8.
 ABI_VERSION = 8     # 8: EV2H_PREC_F16 (one fp16 plane with f16x2's range machinery); 3: F16X2 range records; 4: ev2h_fp_mlp, ev2h_weights.fp1m; 5: window strides of the outputs; 6: ev2h_pack_weights, ev2h_weights.flags; 7: ev2h_sa_desc.xyz_out
 
 PREC = {"f32": 0, "bf16": 1, "f16x2": 2, "bf16x3": 3, "f16": 4}
@@ -113,6 +115,7 @@ EXPORTS = [
     "ev2h_packed_equalization_count", "ev2h_packed_equalization", "ev2h_packed_weight_spread_count", "ev2h_packed_weight_spread", "ev2h_pack_sa_image_bytes", "ev2h_pack_sa_images",
     "ev2h_pack_gemm_image_bytes", "ev2h_pack_gemm_image", "ev2h_plane_unscale",
     "ev2h_event_window_build", "ev2h_event_window_timesort", "ev2h_event_window_sample", "ev2h_joint_metrics", "ev2h_mesh_collisions", "ev2h_mesh_collisions_ws", "ev2h_mesh_collisions_scratch_bytes", "ev2h_collision_penalty",
+    "ev2h_event_window_pixels", "ev2h_demo_point_panels", "ev2h_render_scratch_bytes", "ev2h_render_hands",
 ]
 
 _lib = None
@@ -190,6 +193,12 @@ def lib() -> C.CDLL:
     L.ev2h_mesh_collisions_scratch_bytes.restype = C.c_size_t
     L.ev2h_mesh_collisions_scratch_bytes.argtypes = [ci, ci]
     L.ev2h_collision_penalty.argtypes = [vp, vp, vp, vp, ci, ci, ci, C.c_float, C.c_double, vp, vp, ci, vp, vp]
+    L.ev2h_event_window_pixels.argtypes = [vp, vp, ci, vp, ci, ci, vp, vp, vp, vp]
+    L.ev2h_demo_point_panels.argtypes = [vp, vp, vp, vp, C.c_size_t, ci, ci, ci, ci, vp, ci, ci, ci, vp]
+    L.ev2h_render_scratch_bytes.restype = C.c_size_t
+    L.ev2h_render_scratch_bytes.argtypes = [ci, ci]
+    L.ev2h_render_hands.argtypes = [vp, vp, C.c_size_t, C.c_size_t, vp, ci, vp, vp, ci, ci, ci, ci, ci, C.c_float, C.c_float, C.c_float, C.c_float,
+                                    vp, ci, ci, ci, ci, vp, vp, vp, C.c_size_t, vp]
     L.ev2h_range_report_entries.argtypes = [C.POINTER(C.c_char_p), ci]
     L.ev2h_range_report.argtypes = [vp, ci, ci, vp, vp]
     L.ev2h_profile_set.argtypes = [C.c_char_p, C.POINTER(vp), C.POINTER(vp), ci]

@@ -441,6 +441,38 @@ int ev2h_collision_penalty(const float* verts_left, const float* verts_right, co
                            int B, int nv, int nf, float scale, double sigma, const int32_t* pairs, const int32_t* counts, int max_pairs,
                            double* loss, ev2h_stream_t stream);
 
+/* ---- demo frames: event, segmentation and mesh panels (demo.py:18-68,113-146; dataset/ev2hands_r.py:148-156) -------------- */
+/* What the reference's demo item calls 'coordinates' (ev2hands_r.py:149-154) and the two counts its event_frame is coloured
+ * by: yx [B][N][2] int32 (row, column), pos / neg [B][N] float32, gathered from ev2h_event_window_build's table with the index
+ * clamping of ev2h_event_window_sample (same sample_idx => the same points as its out_cm). */
+int ev2h_event_window_pixels(const float* uniq, const int32_t* uniq_count, int cap, const int32_t* sample_idx, int B, int N,
+                             int32_t* yx, float* pos, float* neg, ev2h_stream_t stream);
+/* Panels 1 and 2 of demo.py:145's np.hstack, written into a uint8 frame [B][height][frame_width][3] at pixel columns event_x0 /
+ * seg_x0 (< 0: panel not written); the panels' background is NOT cleared here (ev2h_render_hands clears it, or the caller).
+ * event_frame (ev2hands_r.py:155-156): bytes 0 and 2 of pixel (y, x) = uint8((p / (p + n)) * 255), uint8((n / (p + n)) * 255),
+ * float32 with one rounding per operation, truncated.  seg_mask (demo.py:35,53-62): class = first maximum of the 4 logits
+ * (logits [B][4][N] float32, window stride logits_stride floats); class 3 sets the pixel's three bytes to 255, class c < 3 byte c.
+ * Bit-identical to the reference's loops; points whose (y, x) is outside the panel are skipped. */
+int ev2h_demo_point_panels(const int32_t* yx, const float* pos, const float* neg, const float* logits, size_t logits_stride,
+                           int B, int N, int width, int height, uint8_t* frame, int frame_width, int event_x0, int seg_x0,
+                           ev2h_stream_t stream);
+/* Panel 3 (demo.py:120-143: both predicted meshes through MAIN_CAMERA, settings.py:42).  The project's OWN renderer -- pyrender's
+ * shader is not reproduced, parity unpinned; tests/ref_render.py is its float64 statement.  verts_* [B][nv][3] float32 metres with
+ * window strides in floats; faces [nfaces][3] int32 into the concatenated 2 nv vertices (left, then right + nv; 2 nv <= 2048);
+ * vf_offsets [2 nv + 1] / vf_faces [vf_len]: the incident faces of every vertex in ascending order (smooth normals are gathered
+ * through it).  Pinhole u = f x / z + cx, v = f y / z + cy, pixel (r, c) sampled at (c + 0.5, r + 0.5); faces with a vertex at
+ * z * 1000 <= znear (mm) are dropped.  The pixel goes to frame [B][height][frame_width][3] at column render_x0 + c as
+ * (0, 0, uint8(I * 255 + 0.5)) BGR, 0 = background; columns [clear_x0, clear_x0 + clear_width) (a multiple of width, not
+ * overlapping the render) are zero-filled by the same launch.  depth [B][height][width] float32 mm (0 = background) and
+ * face_id int32 (-1 = background) are optional.  scratch: device, 16-byte aligned, ev2h_render_scratch_bytes(B, nv) bytes,
+ * used on `stream` only.  Allocates nothing and does not synchronise. */
+size_t ev2h_render_scratch_bytes(int B, int nv);
+int ev2h_render_hands(const float* verts_left, const float* verts_right, size_t stride_left, size_t stride_right,
+                      const int32_t* faces, int nfaces, const int32_t* vf_offsets, const int32_t* vf_faces, int vf_len,
+                      int B, int nv, int width, int height, float f, float cx, float cy, float znear,
+                      uint8_t* frame, int frame_width, int render_x0, int clear_x0, int clear_width,
+                      float* depth, int32_t* face_id, void* scratch, size_t scratch_bytes, ev2h_stream_t stream);
+
 /* ---- whole path -------------------------------------------------------------------------------------- */
 typedef struct ev2h_sa_branch {
     const float* W1x; const float* W2; const float* b2; const float* W3; const float* b3;
