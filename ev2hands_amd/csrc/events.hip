@@ -16,32 +16,8 @@ namespace {
 constexpr int EVW_THREADS = 1024;
 constexpr int EVW_MAX_EVENTS = 32768;
 
-__global__ __launch_bounds__(EVW_THREADS) void event_window_build_kernel(const double* __restrict__ events, const int32_t* __restrict__ offsets,
-                                                                         int width, int height, int cap, int raw_time, int ev_stride,
-                                                                         int32_t* __restrict__ uniq_count, float* __restrict__ uniq) {
-    extern __shared__ __attribute__((aligned(16))) char smem_raw[];
-    unsigned* keys = reinterpret_cast<unsigned*>(smem_raw);
-    __shared__ int s_part[EVW_THREADS];
-    const int b = blockIdx.x, tid = threadIdx.x;
-    const int e0 = offsets[b], E = offsets[b + 1] - e0;
-    if (E <= 0 || E > EVW_MAX_EVENTS) {
-        if (tid == 0) uniq_count[b] = (E <= 0) ? 0 : -1;
-        return;
-    }
-    int n = 1;
-    while (n < E) n <<= 1;
-    const double* ev = events + (size_t)e0 * ev_stride;
-    for (int i = tid; i < n; i += EVW_THREADS) {
-        unsigned k = 0xffffffffu;
-        if (i < E) {
-            const int x = (int)ev[(size_t)i * ev_stride + 0], y = (int)ev[(size_t)i * ev_stride + 1];     // .astype(np.int32): truncation
-            const bool ok = x >= 0 && x < width && y >= 0 && y < height;
-            k = ok ? ((unsigned)(y * width + x) << 15) | (unsigned)i : 0xfffffffeu;           // out-of-sensor events are dropped
-        }
-        keys[i] = k;
-    }
-    __syncthreads();
-    // bitonic sort, ascending
+// ascending bitonic sort of n (a power of two) 32-bit keys in LDS by the whole workgroup
+__device__ __forceinline__ void bitonic_sort_u32(unsigned* keys, int n, int tid) {
     for (int k2 = 2; k2 <= n; k2 <<= 1) {
         for (int j = k2 >> 1; j > 0; j >>= 1) {
             for (int i = tid; i < n; i += EVW_THREADS) {
@@ -55,6 +31,34 @@ __global__ __launch_bounds__(EVW_THREADS) void event_window_build_kernel(const d
             __syncthreads();
         }
     }
+}
+
+// One window by one workgroup: `ev` = its first row, E = its rows.  STREAM_US = false: column 2 holds the times the reference's
+// arrays hold (the caller cut and scaled them); true: rows of a resident recording, column 2 in microseconds -- the kernel applies
+// evaluation_stream.py:102,187 itself, t * 1e-3 rounded, then minus the rounded product of the window's first row (two roundings
+// before the subtraction, never a fused multiply-subtract).  Returns whether the table was built (uniform over the workgroup).
+template <bool STREAM_US>
+__device__ __forceinline__ bool event_window_build_body(const double* __restrict__ ev, int E, int b, int width, int height, int cap, int raw_time,
+                                                        int ev_stride, int32_t* __restrict__ uniq_count, float* __restrict__ uniq,
+                                                        unsigned* keys, int* s_part) {
+    const int tid = threadIdx.x;
+    if (E <= 0 || E > EVW_MAX_EVENTS) {
+        if (tid == 0) uniq_count[b] = (E <= 0) ? 0 : -1;
+        return false;
+    }
+    int n = 1;
+    while (n < E) n <<= 1;
+    for (int i = tid; i < n; i += EVW_THREADS) {
+        unsigned k = 0xffffffffu;
+        if (i < E) {
+            const int x = (int)ev[(size_t)i * ev_stride + 0], y = (int)ev[(size_t)i * ev_stride + 1];     // .astype(np.int32): truncation
+            const bool ok = x >= 0 && x < width && y >= 0 && y < height;
+            k = ok ? ((unsigned)(y * width + x) << 15) | (unsigned)i : 0xfffffffeu;           // out-of-sensor events are dropped
+        }
+        keys[i] = k;
+    }
+    __syncthreads();
+    bitonic_sort_u32(keys, n, tid);
     // run heads -> exclusive scan of head flags over contiguous per-thread chunks
     const int chunk = (n + EVW_THREADS - 1) / EVW_THREADS;
     const int lo = tid * chunk, hi = min(lo + chunk, n);
@@ -73,7 +77,7 @@ __global__ __launch_bounds__(EVW_THREADS) void event_window_build_kernel(const d
     }
     int u = s_part[tid] - heads;                                 // exclusive prefix = index of this thread's first run
     const int total = s_part[EVW_THREADS - 1];
-    const double t0 = raw_time ? 0.0 : ev[2];      // erpc.py accumulates the timestamps as they are, evaluation_stream.py minus the first
+    const double t0 = raw_time ? 0.0 : (STREAM_US ? __dmul_rn(ev[2], 1e-3) : ev[2]);      // erpc.py accumulates the timestamps as they are, evaluation_stream.py minus the first
     float* out = uniq + (size_t)b * cap * 8;
     for (int i = lo; i < hi; ++i) {
         const unsigned k = keys[i];
@@ -87,7 +91,8 @@ __global__ __launch_bounds__(EVW_THREADS) void event_window_build_kernel(const d
             if ((kq >> 15) != pix) break;
             const int e = (int)(kq & 0x7fffu);
             // np.add.at(float32 grid, float64 t): each step adds in float64 and rounds the running sum to float32
-            tsum = (float)((double)tsum + (ev[(size_t)e * ev_stride + 2] - t0));
+            const double te = ev[(size_t)e * ev_stride + 2];
+            tsum = (float)((double)tsum + (STREAM_US ? __dsub_rn(__dmul_rn(te, 1e-3), t0) : te - t0));
             pos += (ev[(size_t)e * ev_stride + 3] == 1.0) ? 1 : 0;
             ++cnt;
         }
@@ -101,6 +106,72 @@ __global__ __launch_bounds__(EVW_THREADS) void event_window_build_kernel(const d
         ++u;
     }
     if (tid == 0) uniq_count[b] = total;
+    return true;
+}
+
+__global__ __launch_bounds__(EVW_THREADS) void event_window_build_kernel(const double* __restrict__ events, const int32_t* __restrict__ offsets,
+                                                                         int width, int height, int cap, int raw_time, int ev_stride,
+                                                                         int32_t* __restrict__ uniq_count, float* __restrict__ uniq) {
+    extern __shared__ __attribute__((aligned(16))) char smem_raw[];
+    __shared__ int s_part[EVW_THREADS];
+    const int b = blockIdx.x;
+    const int e0 = offsets[b];
+    event_window_build_body<false>(events + (size_t)e0 * ev_stride, offsets[b + 1] - e0, b, width, height, cap, raw_time, ev_stride, uniq_count, uniq,
+                                   reinterpret_cast<unsigned*>(smem_raw), s_part);
+}
+
+// The same table for rows starts[b] .. ends[b]-1 of a resident recording (ev2h_event_stream_walk's ranges), plus the window's frame
+// bookkeeping (evaluation_stream.py:183-184,221-222): the frame column is sorted in the same LDS, frame_index = the value of the
+// longest run (the first, i.e. smallest, among equally long ones: values[np.argmax(counts)] of np.unique), first_frame = the smallest.
+__global__ __launch_bounds__(EVW_THREADS) void event_window_build_ranges_kernel(const double* __restrict__ events, int ev_stride, int n_rows,
+                                                                                const int32_t* __restrict__ starts, const int32_t* __restrict__ ends,
+                                                                                int width, int height, int cap, int frame_col,
+                                                                                int32_t* __restrict__ uniq_count, float* __restrict__ uniq,
+                                                                                int32_t* __restrict__ frame_index, int32_t* __restrict__ first_frame) {
+    extern __shared__ __attribute__((aligned(16))) char smem_raw[];
+    unsigned* keys = reinterpret_cast<unsigned*>(smem_raw);
+    __shared__ int s_part[EVW_THREADS];
+    __shared__ unsigned long long s_best[EVW_THREADS];
+    const int b = blockIdx.x, tid = threadIdx.x;
+    const int s = starts[b], e = ends[b];
+    const int E = (s >= 0 && e > s && e <= n_rows) ? e - s : 0;       // a range outside the recording is an empty window
+    const double* ev = events + (size_t)(E ? s : 0) * ev_stride;
+    const bool built = event_window_build_body<true>(ev, E, b, width, height, cap, 0, ev_stride, uniq_count, uniq, keys, s_part);
+    if (!built || frame_col < 0) {
+        if (tid == 0) frame_index[b] = first_frame[b] = -1;           // evaluation_stream.py:95-98: no fifth column
+        return;
+    }
+    __syncthreads();                                                  // the table's last reads of `keys`
+    int n = 1;
+    while (n < E) n <<= 1;
+    for (int i = tid; i < n; i += EVW_THREADS)                        // signed order -> unsigned order; the padding sorts behind row E-1
+        keys[i] = (i < E) ? ((unsigned)(int)ev[(size_t)i * ev_stride + frame_col] ^ 0x80000000u) : 0xffffffffu;
+    __syncthreads();
+    bitonic_sort_u32(keys, n, tid);
+    const int chunk = (E + EVW_THREADS - 1) / EVW_THREADS;
+    const int lo = tid * chunk, hi = min(lo + chunk, E);
+    unsigned long long best = 0;                                      // (run length << 32) | ~key: longest run, smallest value on ties
+    for (int i = lo; i < hi; ++i) {
+        const unsigned k = keys[i];
+        if (i != 0 && keys[i - 1] == k) continue;
+        int a = i, c = E;                                             // first position in (i, E] that holds another value
+        while (c - a > 1) {
+            const int m = a + ((c - a) >> 1);
+            if (keys[m] == k) a = m; else c = m;
+        }
+        const unsigned long long cand = ((unsigned long long)(unsigned)(c - i) << 32) | (unsigned)~k;
+        best = cand > best ? cand : best;
+    }
+    s_best[tid] = best;
+    __syncthreads();
+    for (int off = EVW_THREADS >> 1; off > 0; off >>= 1) {
+        if (tid < off && s_best[tid + off] > s_best[tid]) s_best[tid] = s_best[tid + off];
+        __syncthreads();
+    }
+    if (tid == 0) {
+        frame_index[b] = (int32_t)(~(unsigned)(s_best[0] & 0xffffffffull) ^ 0x80000000u);
+        first_frame[b] = (int32_t)(keys[0] ^ 0x80000000u);
+    }
 }
 
 // Ev2Hands-S (erpc.py:207-211): re-order a window's unique pixels by their mean time (np.argsort; pixels with exactly equal
@@ -208,6 +279,21 @@ extern "C" int ev2h_event_window_build(const double* events, int ev_stride, cons
         EV2H_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(event_window_build_kernel),
                                            hipFuncAttributeMaxDynamicSharedMemorySize, EVW_MAX_EVENTS * 4)););
     event_window_build_kernel<<<B, EVW_THREADS, EVW_MAX_EVENTS * 4, (hipStream_t)stream>>>(events, offsets, width, height, cap, raw_time, ev_stride, uniq_count, uniq);
+    EV2H_CHECK_LAUNCH();
+    return EV2H_OK;
+}
+
+extern "C" int ev2h_event_window_build_ranges(const double* events, int ev_stride, int n_rows, const int32_t* starts, const int32_t* ends, int B,
+                                              int width, int height, int cap, int frame_col, int32_t* uniq_count, float* uniq,
+                                              int32_t* frame_index, int32_t* first_frame, ev2h_stream_t stream) {
+    EV2H_CHECK_ARG(events && starts && ends && uniq_count && uniq && frame_index && first_frame && ev_stride >= 4 && n_rows > 0);
+    EV2H_CHECK_ARG(B > 0 && width > 0 && height > 0 && width * height <= (1 << 17) && cap > 0 && frame_col < ev_stride);
+    static PerDevice attr_set{};
+    EV2H_ONCE_PER_DEVICE(attr_set,
+        EV2H_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(event_window_build_ranges_kernel),
+                                           hipFuncAttributeMaxDynamicSharedMemorySize, EVW_MAX_EVENTS * 4)););
+    event_window_build_ranges_kernel<<<B, EVW_THREADS, EVW_MAX_EVENTS * 4, (hipStream_t)stream>>>(events, ev_stride, n_rows, starts, ends, width, height, cap,
+                                                                                                  frame_col, uniq_count, uniq, frame_index, first_frame);
     EV2H_CHECK_LAUNCH();
     return EV2H_OK;
 }

@@ -38,6 +38,29 @@ class EventWindowBuilder:
         self._last = (ev, off)
         return table, counts
 
+    def accumulate_ranges(self, stream, starts, ends, out=None):
+        """`accumulate` for the windows rows starts[b] .. ends[b]-1 of a resident recording (ev2hands_amd.stream.EventStream; starts /
+        ends device int32 [B], e.g. slices of EventStream.cut()'s): nothing is copied, the kernel reads the recording in place and
+        applies evaluation_stream.py:102,187 to the timestamps itself.  Returns (table, counts, frame_index [B] i32, first_frame [B]
+        i32): table and counts bit for bit those of `accumulate` on the host-cut windows, frame_index the window's most frequent
+        frame (:221-222), first_frame its smallest (:183-184), both -1 for a recording without a frame column.  `out`: such a
+        4-tuple to write into."""
+        if self.raw_time:
+            raise RuntimeError("accumulate_ranges builds evaluation windows (timestamps minus the window's first)")
+        B = int(starts.shape[0])
+        if int(ends.shape[0]) != B or starts.dtype != torch.int32 or ends.dtype != torch.int32 or not (starts.is_contiguous() and ends.is_contiguous()):
+            raise ValueError("starts and ends must be contiguous int32 device tensors of one length")
+        if out is None:
+            out = (torch.empty(B, self.cap, 8, device=self.device, dtype=torch.float32), torch.empty(B, device=self.device, dtype=torch.int32),
+                   torch.empty(B, device=self.device, dtype=torch.int32), torch.empty(B, device=self.device, dtype=torch.int32))
+        table, counts, frame_index, first_frame = out
+        if B:
+            _lib.check(_lib.lib().ev2h_event_window_build_ranges(stream.events.data_ptr(), stream.stride, stream.n_rows, starts.data_ptr(),
+                                                                 ends.data_ptr(), B, self.w, self.h, self.cap, stream.frame_col, counts.data_ptr(),
+                                                                 table.data_ptr(), frame_index.data_ptr(), first_frame.data_ptr(),
+                                                                 _lib.stream_handle()), "ev2h_event_window_build_ranges")
+        return table, counts, frame_index, first_frame
+
     def sample(self, table, counts, sample_idx=None, labels=None):
         """-> float32 [B, 5, N] (and int64 [B, N] labels when the per-pixel `labels` [B, cap] int32 are given).  sample_idx [B, N]
         (any integer type); None draws np.random.choice(M_b, N) per window in batch order from numpy's global RNG

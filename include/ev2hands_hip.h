@@ -402,6 +402,42 @@ int ev2h_event_window_sample(const float* uniq, const int32_t* uniq_count, int c
                              int width, int height, float* out_cm, const int32_t* uniq_labels, int64_t* out_labels,
                              ev2h_stream_t stream);
 
+/* ---- recording -> evaluation windows (dataset/evaluation_stream.py:53-146,177-184; dataset/ev2hands_r.py:96-99) ------------ */
+/* A recording is n_rows (< 2^31: row indices are 32-bit) device float64 rows of ev_stride (>= 4) columns (x, y, t_us, polarity[,
+ * frame index]) in stream order with NON-DECREASING timestamps.  t_ms(i) = t_us[i] * 1e-3 rounded once (get_event, :102);
+ * far(s, j, w) = |t_ms(j) - t_ms(s)| > w in float64.  All results are row indices; they equal the reference's iteration exactly.
+ * ev2h_event_stream_links, for every row i:
+ *   end[i]  = the first j > i with j - i >= min_events and far(i, j, window_ms): a window started at i holds rows i .. end[i]-1
+ *             (get_events_by_time, :124-146); -1 if the recording ends first (StopIteration, :88-91);
+ *   next[i] = i + o + 1 for the first ODD o with far(i, i + o, overlap_ms) -- next_event_time (:61-82) counts every row it reads
+ *             twice and so tests every other row; -1 if such a read runs past the recording;
+ *   *first_bad = the first row whose timestamp is smaller than its predecessor's (or NaN), -1 if there is none.  The links of such
+ *             a recording are in range but meaningless.
+ * The reference's parameters are window_ms 2, overlap_ms 1, min_events 2048 (:10-11,140). */
+int ev2h_event_stream_links(const double* events, int ev_stride, int n_rows, double window_ms, double overlap_ms, int min_events,
+                            int32_t* end, int32_t* next, int32_t* first_bad, ev2h_stream_t stream);
+/* The same end for n caller-chosen starts with a window length each (device arrays; Ev2HandRDataset.__getitem__ draws a start and
+ * randint(1, 3) ms, ev2hands_r.py:96-99): end[k] as end[starts[k]] above with window_ms[k]; -1 also for a start outside the
+ * recording. */
+int ev2h_event_stream_ends(const double* events, int ev_stride, int n_rows, const int32_t* starts, const double* window_ms, int n,
+                           int min_events, int32_t* end, ev2h_stream_t stream);
+/* ERPCParser's iteration (:177-184) over the links: s0 = start, s(k+1) = next[s(k)], kept while end[s(k)] >= 0 AND next[s(k)] >= 0
+ * -- __getitem__ advances before it returns, so the last window of a recording is cut and then dropped when the advance runs out
+ * of rows.  starts / ends [cap] receive the first cap windows; count [3] = (number of windows W -- it may exceed cap --, the
+ * reference's final e_id, *first_bad).  first_bad (optional): if it names a row, W = 0 and nothing is walked.  One launch and no
+ * host synchronisation, whatever W is; W <= n_rows / 2. */
+int ev2h_event_stream_walk(const int32_t* end, const int32_t* next, int n_rows, int start, const int32_t* first_bad, int cap,
+                           int32_t* starts, int32_t* ends, int32_t* count, ev2h_stream_t stream);
+/* ev2h_event_window_build (raw_time = 0) for the B windows rows starts[b] .. ends[b]-1 of a recording (device arrays, e.g. slices of
+ * ev2h_event_stream_walk's): the kernel scales and shifts the timestamps itself, t_ms(i) - t_ms(starts[b]) with both products
+ * rounded first (:102,187), and writes the table and count that ev2h_event_window_build writes for the host-cut, host-scaled copy
+ * of those rows, bit for bit (-1 above 32768 rows; 0 for a range that is empty or outside the recording).  frame_col >= 4: column
+ * of the frame index; frame_index [B] = its most frequent value in the window, the smallest on ties (:221-222), first_frame [B] =
+ * its smallest value (the row of `joints` that :183-184 picks).  Both are -1 when frame_col < 0 (:95-98) or no table was built. */
+int ev2h_event_window_build_ranges(const double* events, int ev_stride, int n_rows, const int32_t* starts, const int32_t* ends, int B,
+                                   int width, int height, int cap, int frame_col, int32_t* uniq_count, float* uniq,
+                                   int32_t* frame_index, int32_t* first_frame, ev2h_stream_t stream);
+
 /* ---- per-frame joint metrics (next row 8f-3; evaluate.py:185-234, evaluate_ev2hands_r.py:35-89) ------------------------ */
 /* j3d_left / j3d_right [B][21][3] float32 metres (the forward's outputs); j3d_gts [B][G][2][21][3] float64 metres (G ground-truth
  * candidates per frame).  For the candidate with the best rounded right-root-relative AUC (first on ties): pck [B][3][num_steps+1]
