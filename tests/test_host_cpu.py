@@ -46,6 +46,44 @@ def test_workspace_size_grows_linearly(built):
     assert built.ev2h_workspace_bytes(0, 2048) == 0
 
 
+def workspace_layout(built, B, N, names):
+    """(total bytes, [[offset, count] per name]) as the library resolves them; neither call touches the device"""
+    base = 1 << 20                      # any non-null base: the accessor only adds the offset to it
+    rows = []
+    for name in names:
+        cnt = C.c_size_t(0)
+        p = built.ev2h_workspace_buffer(base, B, N, name.encode(), C.byref(cnt))
+        assert p, f"{name} does not resolve at ({B}, {N})"
+        rows.append([p - base, cnt.value])
+    return built.ev2h_workspace_bytes(B, N), rows
+
+
+def test_workspace_layout_is_pinned(built):
+    """The workspace layout is ABI-adjacent (hosts size their allocation by it, debuggers and the tests address buffers by name):
+    every buffer name and every `rng.` record resolves to the offset and count recorded in tests/workspace_layout.json, and the
+    totals are the recorded ones, at four shapes.  The table was written from the library as it was before the workspace got typed
+    buffer ids; an unknown name and an unknown range record still resolve to NULL."""
+    import json
+    with open(os.path.join(ROOT, "tests", "workspace_layout.json")) as f:
+        table = json.load(f)
+    names = table["names"]
+    assert len(names) == 95 and len(set(names)) == 95 and sum(n.startswith("rng.") for n in names) == 32
+    assert sorted(table["shapes"]) == sorted(["1x128", "8x2048", "256x2048", "16x8192"])
+    for shape, want in table["shapes"].items():
+        B, N = (int(v) for v in shape.split("x"))
+        total, rows = workspace_layout(built, B, N, names)
+        assert total == want["total"], (shape, total, want["total"])
+        for name, got, exp in zip(names, rows, want["offset_count"]):
+            assert got == exp, (shape, name, got, exp)
+        assert max(o + 4 * c for o, c in rows) <= total
+    assert table["shapes"]["1x128"]["total"] == 6400256 and table["shapes"]["8x2048"]["total"] == 184448768
+    assert table["shapes"]["256x2048"]["total"] == 5902354432 and table["shapes"]["16x8192"]["total"] == 1221782784
+    cnt = C.c_size_t(0)
+    for unknown in (b"l1cat_", b"", b"rng.", b"rng.nosuch", b"rng.l1cat", b"ranges_"):
+        assert not built.ev2h_workspace_buffer(1 << 20, 8, 2048, unknown, C.byref(cnt)), unknown
+        assert not built.ev2h_workspace_buffer_ex(1 << 20, 8, 2048, unknown, C.byref(cnt), None), unknown
+
+
 def test_bad_arguments_return_error_codes_not_crashes(built):
     d = _lib.GemmDesc()
     assert built.ev2h_gemm(C.byref(d), None) != 0
