@@ -10,6 +10,7 @@
 // sequentially in fp32 by the thread that owns its first element, and the runs come out already in np.nonzero order.
 #include "common.hpp"
 #include "ev2hands_hip.h"
+#include "random.hpp"
 
 namespace {
 
@@ -268,6 +269,60 @@ __global__ __launch_bounds__(256) void event_window_sample_kernel(const float* _
     }
 }
 
+// event_window_sample_kernel with the index DRAWN here (random.hpp, stream 0) instead of read from memory: draw n of window
+// window_ids[b] is a function of (seed, window id, n) alone.  The normalisation is the same sequence of float32 operations.  A
+// window whose M lies outside [1, cap] cannot be sampled: its id goes into *status (atomicMin; the caller starts it at INT32_MAX)
+// and its outputs are zeros.
+__global__ __launch_bounds__(256) void event_window_sample_seeded_kernel(const float* __restrict__ uniq, const int32_t* __restrict__ uniq_count, int cap,
+                                                                         unsigned long long seed, const int32_t* __restrict__ window_ids, int N,
+                                                                         int width, int height, float* __restrict__ out_cm,
+                                                                         int32_t* __restrict__ sample_idx_out, const int32_t* __restrict__ uniq_labels,
+                                                                         int64_t* __restrict__ out_labels, int32_t* __restrict__ status) {
+    __shared__ float s_min[256], s_max[256];
+    const int b = blockIdx.x, tid = threadIdx.x;
+    const int M = uniq_count[b];
+    const int32_t wid = window_ids[b];
+    float* o = out_cm + (size_t)b * 5 * N;
+    if (M < 1 || M > cap) {                                       // uniform over the workgroup
+        if (tid == 0) atomicMin(status, wid);
+        for (int n = tid; n < N; n += 256) {
+#pragma unroll
+            for (int c = 0; c < 5; ++c) o[c * (size_t)N + n] = 0.f;
+            if (sample_idx_out) sample_idx_out[(size_t)b * N + n] = 0;
+            if (out_labels) out_labels[(size_t)b * N + n] = 0;
+        }
+        return;
+    }
+    const float* tab = uniq + (size_t)b * cap * 8;
+    float mn = INFINITY, mx = -INFINITY;
+    for (int n = tid; n < N; n += 256) {
+        const int i = ev2h_random::sample_index(seed, (uint32_t)wid, (uint32_t)n, (uint32_t)M);
+        const float t = tab[(size_t)i * 8 + 2];
+        mn = fminf(mn, t);
+        mx = fmaxf(mx, t);
+    }
+    s_min[tid] = mn; s_max[tid] = mx;
+    __syncthreads();
+    for (int off = 128; off > 0; off >>= 1) {
+        if (tid < off) { s_min[tid] = fminf(s_min[tid], s_min[tid + off]); s_max[tid] = fmaxf(s_max[tid], s_max[tid + off]); }
+        __syncthreads();
+    }
+    const float tmin = s_min[0], tmax = s_max[0];
+    const float range = __fsub_rn(tmax, tmin);
+    for (int n = tid; n < N; n += 256) {
+        const int i = ev2h_random::sample_index(seed, (uint32_t)wid, (uint32_t)n, (uint32_t)M);      // drawn again: cheaper than keeping N indices
+        const float4 r0 = *reinterpret_cast<const float4*>(tab + (size_t)i * 8);
+        const float neg = tab[(size_t)i * 8 + 4];
+        o[0 * (size_t)N + n] = __fsub_rn(__fmul_rn(2.f, __fdiv_rn(r0.x, (float)width)), 1.f);
+        o[1 * (size_t)N + n] = __fsub_rn(__fmul_rn(2.f, __fdiv_rn(r0.y, (float)height)), 1.f);
+        o[2 * (size_t)N + n] = __fsub_rn(__fmul_rn(2.f, __fdiv_rn(__fsub_rn(r0.z, tmin), range)), 1.f);
+        o[3 * (size_t)N + n] = r0.w;
+        o[4 * (size_t)N + n] = neg;
+        if (sample_idx_out) sample_idx_out[(size_t)b * N + n] = i;
+        if (out_labels) out_labels[(size_t)b * N + n] = uniq_labels ? (int64_t)uniq_labels[(size_t)b * cap + i] : 0;
+    }
+}
+
 }  // namespace
 
 extern "C" int ev2h_event_window_build(const double* events, int ev_stride, const int32_t* offsets, int B, int width, int height, int cap,
@@ -320,6 +375,17 @@ extern "C" int ev2h_event_window_sample(const float* uniq, const int32_t* uniq_c
     EV2H_CHECK_ARG(B > 0 && N > 0 && cap > 0 && width > 0 && height > 0);
     event_window_sample_kernel<<<B, 256, 0, (hipStream_t)stream>>>(uniq, uniq_count, cap, sample_idx, N, width, height, out_cm, uniq_labels,
                                                                    out_labels);
+    EV2H_CHECK_LAUNCH();
+    return EV2H_OK;
+}
+
+extern "C" int ev2h_event_window_sample_seeded(const float* uniq, const int32_t* uniq_count, int cap, uint64_t seed, const int32_t* window_ids,
+                                               int B, int N, int width, int height, float* out_cm, int32_t* sample_idx_out,
+                                               const int32_t* uniq_labels, int64_t* out_labels, int32_t* status, ev2h_stream_t stream) {
+    EV2H_CHECK_ARG(uniq && uniq_count && window_ids && out_cm && status);
+    EV2H_CHECK_ARG(B > 0 && N > 0 && cap > 0 && width > 0 && height > 0);
+    event_window_sample_seeded_kernel<<<B, 256, 0, (hipStream_t)stream>>>(uniq, uniq_count, cap, (unsigned long long)seed, window_ids, N, width, height,
+                                                                          out_cm, sample_idx_out, uniq_labels, out_labels, status);
     EV2H_CHECK_LAUNCH();
     return EV2H_OK;
 }

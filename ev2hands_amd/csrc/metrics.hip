@@ -17,7 +17,7 @@ struct MetP {
     float* pck;                                // [B][3][steps+1]
     double* auc;                               // [B][3]  (unrounded)
     double* mpjpe; double* rootd;              // [B]
-    int32_t* best;                             // [B]
+    int32_t* best;                             // [B], optional
 };
 
 __device__ __forceinline__ double wave_sum_f64(double v) {
@@ -37,8 +37,9 @@ __device__ __forceinline__ double wave_min_f64(double v) {
     return v;
 }
 
-__global__ __launch_bounds__(64) void joint_metrics_kernel(MetP p) {
-    const int b = blockIdx.x, lane = threadIdx.x;
+// One frame by one wavefront.  `gts` = the frame's G candidates [G][2][21][3]; shared by the two kernels below.
+__device__ __forceinline__ void joint_metrics_frame(const MetP& p, int b, const double* __restrict__ gts) {
+    const int lane = threadIdx.x;
     const bool act = lane < 42;
     const int hand = act ? lane / 21 : 0, j = act ? lane % 21 : 0;
     const float* src = (hand ? p.right : p.left) + ((size_t)b * 21 + j) * 3;
@@ -63,7 +64,7 @@ __global__ __launch_bounds__(64) void joint_metrics_kernel(MetP p) {
     for (int pass = 0; pass < 2; ++pass) {
         const int g0 = pass ? best : 0, g1 = pass ? best + 1 : p.G;
         for (int g = g0; g < g1; ++g) {
-            const double* gs = p.gts + ((((size_t)b * p.G + g) * 2 + hand) * 21 + j) * 3;
+            const double* gs = gts + (((size_t)g * 2 + hand) * 21 + j) * 3;
             const double gx = gs[0] * 1000.0, gy = gs[1] * 1000.0, gz = gs[2] * 1000.0;
             const double grx = bcast(gx, own_root), gry = bcast(gy, own_root), grz = bcast(gz, own_root);
             const double gRx = bcast(gx, 21), gRy = bcast(gy, 21), gRz = bcast(gz, 21);
@@ -105,15 +106,36 @@ __global__ __launch_bounds__(64) void joint_metrics_kernel(MetP p) {
                 }
                 const double m = wave_sum_f64(act ? d[1] : 0.0) / 42.0;
                 // root distance: min over joints of |gt_left[j] - gt_right[j]| for the chosen candidate
-                const double* gl = p.gts + ((((size_t)b * p.G + g) * 2 + 0) * 21 + (lane % 21)) * 3;
+                const double* gl = gts + (((size_t)g * 2 + 0) * 21 + (lane % 21)) * 3;
                 const double* gr = gl + 21 * 3;
                 const double ex = (gl[0] - gr[0]) * 1.0, ey = gl[1] - gr[1], ez = gl[2] - gr[2];
                 const double dd = sqrt((ex * 1000.0) * (ex * 1000.0) + (ey * 1000.0) * (ey * 1000.0) + (ez * 1000.0) * (ez * 1000.0));
                 const double rmin = wave_min_f64(lane < 21 ? dd : 1e300);
-                if (lane == 0) { p.mpjpe[b] = m; p.rootd[b] = rmin; p.best[b] = g; }
+                if (lane == 0) { p.mpjpe[b] = m; p.rootd[b] = rmin; if (p.best) p.best[b] = g; }
             }
         }
     }
+}
+
+__global__ __launch_bounds__(64) void joint_metrics_kernel(MetP p) {
+    joint_metrics_frame(p, blockIdx.x, p.gts + (size_t)blockIdx.x * p.G * (2 * 21 * 3));
+}
+
+// The same with the ground truth looked up here: the one candidate of frame b is row first_frame[b] of a joints table
+// [F][2][21][3] (evaluation_stream.py:148-157,183-184: np.unique sorts and [:1] keeps the smallest frame, so G = 1).  A row outside
+// the table: has_gt = 0, the frame's outputs are zeros and nothing is read.
+__global__ __launch_bounds__(64) void joint_metrics_frames_kernel(MetP p, const int32_t* __restrict__ first_frame, int F, int32_t* __restrict__ has_gt) {
+    const int b = blockIdx.x, lane = threadIdx.x;
+    const int f = first_frame[b];
+    if (f < 0 || f >= F) {                                        // uniform over the wavefront
+        const int n = p.steps + 1;
+        for (int i = lane; i < 3 * n; i += 64) p.pck[(size_t)b * 3 * n + i] = 0.f;
+        if (lane < 3) p.auc[(size_t)b * 3 + lane] = 0.0;
+        if (lane == 0) { p.mpjpe[b] = 0.0; p.rootd[b] = 0.0; has_gt[b] = 0; }
+        return;
+    }
+    if (lane == 0) has_gt[b] = 1;
+    joint_metrics_frame(p, b, p.gts + (size_t)f * (2 * 21 * 3));
 }
 
 }  // namespace
@@ -125,6 +147,17 @@ extern "C" int ev2h_joint_metrics(const float* j3d_left, const float* j3d_right,
     EV2H_CHECK_ARG(B > 0 && G > 0 && num_steps > 0 && dist_max_mm > 0);
     MetP p{j3d_left, j3d_right, j3d_gts, B, G, num_steps, dist_max_mm, pck, auc, mpjpe, root_distance, best};
     joint_metrics_kernel<<<B, 64, 0, (hipStream_t)stream>>>(p);
+    EV2H_CHECK_LAUNCH();
+    return EV2H_OK;
+}
+
+extern "C" int ev2h_joint_metrics_frames(const float* j3d_left, const float* j3d_right, const double* joints, int F, const int32_t* first_frame,
+                                         int B, int num_steps, double dist_max_mm, float* pck, double* auc, double* mpjpe,
+                                         double* root_distance, int32_t* has_gt, ev2h_stream_t stream) {
+    EV2H_CHECK_ARG(j3d_left && j3d_right && joints && first_frame && pck && auc && mpjpe && root_distance && has_gt);
+    EV2H_CHECK_ARG(B > 0 && F > 0 && num_steps > 0 && dist_max_mm > 0);
+    MetP p{j3d_left, j3d_right, joints, B, 1, num_steps, dist_max_mm, pck, auc, mpjpe, root_distance, nullptr};
+    joint_metrics_frames_kernel<<<B, 64, 0, (hipStream_t)stream>>>(p, first_frame, F, has_gt);
     EV2H_CHECK_LAUNCH();
     return EV2H_OK;
 }

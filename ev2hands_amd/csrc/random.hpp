@@ -1,0 +1,56 @@
+// Counter-based random draws on the device: Philox4x32-10 (Salmon, Moraes, Dror, Shaw: "Parallel random
+// numbers: as easy as 1, 2, 3", SC'11).  A draw is a pure function of (seed, window id, stream, position): it does not depend on
+// the batch a window is in, on its place in that batch, or on any draw made before.  tests/ref_philox.py is the NumPy restatement
+// the kernels agree with bit for bit, held to the published known answers.
+//
+//   key     = (seed & 0xffffffff, seed >> 32), seed an unsigned 64-bit integer
+//   counter = (block, window_id, stream, 0); one block is four 32-bit words
+//   stream 0, the resampling indices: draw n of a window is word n % 4 of block n / 4
+//   stream 1, the four farthest-point-sampling seeds: block 0, words 0..3 = enc.sa1, enc.sa2, left.sa1, right.sa1
+//   a 32-bit word u becomes an index below M by multiply-shift, (u * M) >> 32 in 64 bits.  There is NO rejection step, so the
+//   indices are not exactly uniform: some values are hit by ceil(2^32 / M) words and the others by floor(2^32 / M), a relative
+//   bias of at most M / 2^32 -- below 7.7e-6 for M <= 32768 (the largest table a window can have).
+#pragma once
+#include <stdint.h>
+
+#include <hip/hip_runtime.h>
+
+namespace ev2h_random {
+
+constexpr uint32_t PHILOX_M0 = 0xD2511F53u, PHILOX_M1 = 0xCD9E8D57u;        // round multipliers
+constexpr uint32_t PHILOX_W0 = 0x9E3779B9u, PHILOX_W1 = 0xBB67AE85u;        // key increments (Weyl sequence)
+constexpr uint32_t STREAM_SAMPLE = 0, STREAM_FPS = 1;
+
+struct u32x4 { uint32_t v[4]; };
+
+__device__ __forceinline__ u32x4 philox4x32_10(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, uint32_t k0, uint32_t k1) {
+#pragma unroll
+    for (int r = 0; r < 10; ++r) {
+        const uint32_t hi0 = __umulhi(PHILOX_M0, c0), lo0 = PHILOX_M0 * c0;
+        const uint32_t hi1 = __umulhi(PHILOX_M1, c2), lo1 = PHILOX_M1 * c2;
+        c0 = hi1 ^ c1 ^ k0;
+        c1 = lo1;
+        c2 = hi0 ^ c3 ^ k1;
+        c3 = lo0;
+        k0 += PHILOX_W0;
+        k1 += PHILOX_W1;
+    }
+    return u32x4{{c0, c1, c2, c3}};
+}
+
+__device__ __forceinline__ u32x4 window_block(uint64_t seed, uint32_t window_id, uint32_t stream, uint32_t block) {
+    return philox4x32_10(block, window_id, stream, 0u, (uint32_t)(seed & 0xffffffffull), (uint32_t)(seed >> 32));
+}
+
+// u -> [0, bound): the high word of the 64-bit product
+__device__ __forceinline__ uint32_t bounded(uint32_t u, uint32_t bound) { return (uint32_t)(((uint64_t)u * (uint64_t)bound) >> 32); }
+
+// resampling index n of a window with M unique pixels
+__device__ __forceinline__ int sample_index(uint64_t seed, uint32_t window_id, uint32_t n, uint32_t M) {
+    const u32x4 b = window_block(seed, window_id, STREAM_SAMPLE, n >> 2);
+    const uint32_t w = n & 3u;
+    const uint32_t u = w == 0 ? b.v[0] : w == 1 ? b.v[1] : w == 2 ? b.v[2] : b.v[3];      // selects, not an indexed (scratch) read
+    return (int)bounded(u, M);
+}
+
+}  // namespace ev2h_random

@@ -5,7 +5,8 @@ Mirrors what the reference's dataset classes do per item on the CPU
 variant dataset/erpc.py:169-249 is EventWindowBuilderS), batched on the GPU
 through ev2h_event_window_build / ev2h_event_window_timesort / ev2h_event_window_sample.  The resampling indices are drawn on the host with
 np.random.choice(M, N) per window, like the reference, which needs the unique-pixel counts M back from the device (one
-small copy); pass `sample_idx` to avoid that synchronisation.
+small copy); pass `sample_idx` to avoid that synchronisation, or use `sample_seeded`, which draws them on the device with the
+project's own counter-based generator (csrc/random.hpp).
 """
 from __future__ import annotations
 
@@ -80,6 +81,44 @@ class EventWindowBuilder:
                                               self.h, out.data_ptr(), _lib.ptr(labels), _lib.ptr(lab), _lib.stream_handle()),
                    "ev2h_event_window_sample")
         return out if labels is None else (out, lab)
+
+    def sample_seeded(self, table, counts, seed: int, window_ids, labels=None, return_idx: bool = False, status=None, out=None):
+        """`sample` with the indices drawn on the device by a counter-based generator (csrc/random.hpp) instead of
+        np.random.choice on the host: draw n of window window_ids[b] depends on (seed, window id, n) alone -- not on the batch the
+        window is in, nor on any earlier draw -- and `counts` never leaves the device.  This is the project's own, opt-in draw; it is
+        not bit-compatible with numpy's generator (`sample` remains the reference-order path).
+        seed: 0 .. 2**64-1.  window_ids: contiguous device int32 [B].  status: device int32 [1] that the caller set to 2**31-1; it
+        receives the smallest id of a window that could not be sampled (count outside [1, cap]; such a window's tensor is zeros).
+        Without one, a fresh status is checked here, which costs a host synchronisation.  out: float32 [B, 5, N] to write into.
+        return_idx: True, or an int32 [B, N] device tensor that receives the drawn indices.
+        -> events [B, 5, N] (, labels [B, N] int64 with `labels`) (, the indices [B, N] int32 with return_idx)."""
+        B = int(table.shape[0])
+        if window_ids.dtype != torch.int32 or window_ids.device != table.device or not window_ids.is_contiguous() or tuple(window_ids.shape) != (B,):
+            raise ValueError("window_ids must be a contiguous int32 device tensor [B]")
+        if not 0 <= int(seed) < 2 ** 64:
+            raise ValueError("seed must be an unsigned 64-bit integer")
+        own_status = status is None
+        if own_status:
+            status = torch.full((1,), 2 ** 31 - 1, device=self.device, dtype=torch.int32)
+        elif status.dtype != torch.int32 or status.device != table.device or status.numel() != 1:
+            raise ValueError("status must be a device int32 tensor with one element")
+        n = self.n
+        if out is None:
+            out = torch.empty(B, 5, n, device=self.device, dtype=torch.float32)
+        elif tuple(out.shape) != (B, 5, n) or out.dtype != torch.float32 or not out.is_contiguous():
+            raise ValueError(f"out must be a contiguous float32 [{B}, 5, {n}] tensor")
+        lab = torch.empty(B, n, device=self.device, dtype=torch.int64) if labels is not None else None
+        idx = torch.empty(B, n, device=self.device, dtype=torch.int32) if return_idx is True else (return_idx if torch.is_tensor(return_idx) else None)
+        if B:
+            _lib.check(_lib.lib().ev2h_event_window_sample_seeded(table.data_ptr(), counts.data_ptr(), self.cap, int(seed), window_ids.data_ptr(), B, n,
+                                                                  self.w, self.h, out.data_ptr(), _lib.ptr(idx), _lib.ptr(labels), _lib.ptr(lab),
+                                                                  status.data_ptr(), _lib.stream_handle()), "ev2h_event_window_sample_seeded")
+        if own_status:
+            bad = int(status.item())
+            if bad != 2 ** 31 - 1:
+                raise RuntimeError(f"window {bad} is empty, exceeds 32768 events or has more unique pixels than `cap`")
+        res = (out,) + ((lab,) if labels is not None else ()) + ((idx,) if idx is not None else ())
+        return res[0] if len(res) == 1 else res
 
     def __call__(self, windows, sample_idx=None):
         table, counts = self.accumulate(windows)

@@ -213,6 +213,26 @@ class TEHNet(nn.Module):
         return [torch.randint(0, hi, (B,), dtype=torch.long) for hi in (N, synth.SA1_NPOINT, N, N)]
 
     @staticmethod
+    def seeded_fps_init(seed: int, window_ids: torch.Tensor, N: int, out: torch.Tensor | None = None) -> torch.Tensor:
+        """The same four start points drawn on the DEVICE by the counter-based generator (csrc/random.hpp): window
+        window_ids[b]'s four values depend on (seed, window id) alone, whatever batch it is in.  window_ids: contiguous device int32
+        [B].  Returns [4, B] int64 on the device -- assign it to `fps_init`; _inits_to_device takes it as it is.  The project's own
+        opt-in draw, not bit-compatible with torch's generator (draw_fps_init remains the reference-order path)."""
+        B = int(window_ids.shape[0])
+        if window_ids.dtype != torch.int32 or not window_ids.is_cuda or not window_ids.is_contiguous() or window_ids.dim() != 1:
+            raise ValueError("window_ids must be a contiguous int32 device tensor [B]")
+        if not 0 <= int(seed) < 2 ** 64:
+            raise ValueError("seed must be an unsigned 64-bit integer")
+        if out is None:
+            out = torch.empty(4, B, dtype=torch.long, device=window_ids.device)
+        elif tuple(out.shape) != (4, B) or out.dtype != torch.long or not out.is_contiguous():
+            raise ValueError(f"out must be a contiguous int64 [4, {B}] tensor")
+        if B:
+            _lib.check(_lib.lib().ev2h_fps_init_seeded(int(seed), window_ids.data_ptr(), B, int(N), synth.SA1_NPOINT, out.data_ptr(),
+                                                       _lib.stream_handle()), "ev2h_fps_init_seeded")
+        return out
+
+    @staticmethod
     def _inits_to_device(inits, device) -> torch.Tensor:
         """[4, B] int64 on the device.  Host tensors -- the reference's own case: torch.randint on the CPU generator,
         pointnet2_utils.py:75 -- go through PINNED memory: an "asynchronous" copy out of pageable memory blocks the host until the

@@ -402,6 +402,16 @@ int ev2h_event_window_timesort(const float* uniq_in, const int32_t* uniq_count, 
 int ev2h_event_window_sample(const float* uniq, const int32_t* uniq_count, int cap, const int32_t* sample_idx, int B, int N,
                              int width, int height, float* out_cm, const int32_t* uniq_labels, int64_t* out_labels,
                              ev2h_stream_t stream);
+/* The same resampling with the indices drawn in the kernel instead of read from memory (evaluation_stream.py:209 draws them with
+ * np.random.choice from the global host generator, in batch order): draw n of window window_ids[b] (device int32 [B]) is word
+ * n % 4 of Philox4x32-10 block n / 4 under key (seed & 0xffffffff, seed >> 32) and counter (block, window id, 0, 0), reduced to
+ * [0, M) by (u * M) >> 32 -- a function of (seed, window id, n) alone, whatever batch the window is in (csrc/random.hpp; no
+ * rejection step, bias <= M / 2^32).  The normalisation is ev2h_event_window_sample's, operation for operation.  sample_idx_out
+ * [B][N] int32 (optional) receives the indices.  A window whose M = uniq_count[b] lies outside [1, cap] cannot be sampled: its
+ * outputs are zeros and *status (device int32, set to INT32_MAX by the caller) receives the smallest such window id (atomicMin). */
+int ev2h_event_window_sample_seeded(const float* uniq, const int32_t* uniq_count, int cap, uint64_t seed, const int32_t* window_ids,
+                                    int B, int N, int width, int height, float* out_cm, int32_t* sample_idx_out,
+                                    const int32_t* uniq_labels, int64_t* out_labels, int32_t* status, ev2h_stream_t stream);
 
 /* ---- recording -> evaluation windows (dataset/evaluation_stream.py:53-146,177-184; dataset/ev2hands_r.py:96-99) ------------ */
 /* A recording is n_rows (< 2^31: row indices are 32-bit) device float64 rows of ev_stride (>= 4) columns (x, y, t_us, polarity[,
@@ -447,6 +457,35 @@ int ev2h_event_window_build_ranges(const double* events, int ev_stride, int n_ro
 int ev2h_joint_metrics(const float* j3d_left, const float* j3d_right, const double* j3d_gts, int B, int G, int num_steps,
                        double dist_max_mm, float* pck, double* auc, double* mpjpe, double* root_distance, int32_t* best,
                        ev2h_stream_t stream);
+/* ev2h_joint_metrics with the ground truth looked up on the device: joints [F][2][21][3] float64 metres is a recording's table,
+ * and the ONE candidate of window b is its row first_frame[b] (device int32 [B], ev2h_event_window_build_ranges') -- np.unique
+ * sorts the window's frame values and [:1] keeps the smallest (evaluation_stream.py:148-157,183-184), so G = 1.  has_gt [B] = 0
+ * where first_frame[b] lies outside [0, F): that window's outputs are zeros and nothing is read.  pck, auc, mpjpe and
+ * root_distance as above. */
+int ev2h_joint_metrics_frames(const float* j3d_left, const float* j3d_right, const double* joints, int F, const int32_t* first_frame,
+                              int B, int num_steps, double dist_max_mm, float* pck, double* auc, double* mpjpe,
+                              double* root_distance, int32_t* has_gt, ev2h_stream_t stream);
+
+/* ---- a whole recording's metrics, accumulated on the device (evaluate_ev2hands_r.py:185-266; model/pointnet2_utils.py:75) ---- */
+/* The four farthest-point-sampling start points of B windows, drawn like ev2h_event_window_sample_seeded's indices: words 0..3 of
+ * block 0 under counter (0, window id, 1, 0), in the reference's order (enc.sa1, enc.sa2, left.sa1, right.sa1) with bounds
+ * (N, sa1_npoint, N, N).  out: device int64 [4][B], the layout ev2h_forward's fps_init takes. */
+int ev2h_fps_init_seeded(uint64_t seed, const int32_t* window_ids, int B, int N, int sa1_npoint, int64_t* out, ev2h_stream_t stream);
+/* Folds one batch of per-frame results (ev2h_joint_metrics_frames' outputs, the capped collision counts, the windows' frame_index
+ * and ids) into caller-owned device state, zeroed before the first call except scalars = (0, -1):
+ *   sums [3 * (num_steps + 1) + 1] float64: the three PCK curves summed over the frames (:210-212), then the joint loss (:213);
+ *   frame_joint_loss, frame_root_distance [w_cap] float64, frame_auc [3][w_cap] float64 (unrounded), frame_collisions,
+ *   frame_frame_index [w_cap] int32: the frames of this batch at positions offset .. offset + B - 1 (offset + B <= w_cap);
+ *   scalars [2] int32: frames scored so far, and stopped_at = the id of the first window without ground truth, -1 if none.
+ * Windows at or behind the first one with has_gt = 0, in this or an earlier call, are not accumulated: the reference's iteration
+ * ends there (evaluation_stream.py:152-155).  The sums are carried across calls and, within a call, added in window order by one
+ * thread per curve point: the totals equal a sequential float64 loop over the frames bit for bit, whatever the batch size.
+ * One launch, no host synchronisation, capturable. */
+int ev2h_eval_accumulate(const float* pck, const double* auc, const double* mpjpe, const double* root_distance, const int32_t* has_gt,
+                         const int32_t* collisions, const int32_t* frame_index, const int32_t* window_ids, int B, int num_steps,
+                         int offset, int w_cap, double* sums, double* frame_joint_loss, double* frame_root_distance,
+                         double* frame_auc, int32_t* frame_collisions, int32_t* frame_frame_index, int32_t* scalars,
+                         ev2h_stream_t stream);
 
 /* ---- two-hand mesh self-collision (next row 8f-4; evaluate_ev2hands_r.py:128-160, utils/__init__.py:106-124) ---------------- */
 /* verts_left / verts_right [B][nv][3] float32 metres (the forward's vertices), faces [nf][3] int32 (nv <= 778, nf <= 1538).
