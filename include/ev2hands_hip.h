@@ -413,6 +413,34 @@ int ev2h_event_window_sample_seeded(const float* uniq, const int32_t* uniq_count
                                     int B, int N, int width, int height, float* out_cm, int32_t* sample_idx_out,
                                     const int32_t* uniq_labels, int64_t* out_labels, int32_t* status, ev2h_stream_t stream);
 
+/* ---- raw recording -> undistorted events (dataset/evaluation_stream.py:40-41, src/camera.py:157-168) ----------------------- */
+/* camera.undistort on every event of a recording, in place: events are n_rows (< 2^31) device float64 rows of ev_stride (4 or 5)
+ * columns with x, y in columns 0 and 1; the other columns are neither read nor written.  camera_matrix (9 doubles, row-major K)
+ * and dist (n_dist = 4, 5, 8 or 12 doubles) are HOST arrays read during the call; they reach the kernel by value.  Per event, every
+ * operation one rounded float64 operation in the order written:
+ *   u, v = x, y rounded to float32 (xy.astype(np.float32), :40), widened to double
+ *   fx, fy, cx, cy = K[0][0], K[1][1], K[0][2], K[1][2]            (cv2.undistortPoints ignores the skew K[0][1] here)
+ *   x = x0 = (u - cx) * (1 / fx),  y = y0 = (v - cy) * (1 / fy)
+ *   k[0..11] = (k1, k2, p1, p2, k3, k4, k5, k6, s1, s2, s3, s4), zero where absent
+ *   EXACTLY 5 times (OpenCV's default criteria: MAX_ITER 5, no epsilon test; the count is part of the result):
+ *     r2     = x*x + y*y
+ *     icdist = (1 + ((k[7]*r2 + k[6])*r2 + k[5])*r2) / (1 + ((k[4]*r2 + k[1])*r2 + k[0])*r2)
+ *     if icdist < 0:  x = (u - cx) / fx,  y = (v - cy) / fy,  stop iterating
+ *     dX = 2*k[2]*x*y + k[3]*(r2 + 2*x*x) + k[8]*r2 + k[9]*r2*r2
+ *     dY = k[2]*(r2 + 2*y*y) + 2*k[3]*x*y + k[10]*r2 + k[11]*r2*r2
+ *     x  = (x0 - dX) * icdist,  y = (y0 - dY) * icdist
+ *   x, y rounded to float32 (cv2 returns CV_32FC2 for float32 input), widened to double
+ *   x' = K[0][0]*x + K[0][1]*y + K[0][2],  y' = K[1][0]*x + K[1][1]*y + K[1][2]      (the FULL K: `und @ mtx.T`, camera.py:160)
+ *   x' clipped to [0, width - 1], y' to [0, height - 1] (:164-165); a NaN stays a NaN.
+ * The OpenCV part is public OpenCV 4.x as recalled; cv2 itself is not available to this project's tests, so parity with cv2 is
+ * UNPINNED (tests/ref_undistort.py is the float64 restatement the kernel is held to).
+ * *first_bad (device int32) = the smallest row whose x or y, or whose x' or y' before the clip, is not finite (the reference's
+ * assert at :166 fails on such a row), -1 if there is none (atomicMin).
+ * EV2H_ERR_ARG: n_dist not in {4, 5, 8, 12} (14 is the tilted-sensor model, not provided), a K whose last row is not (0, 0, 1)
+ * (:161), fx or fy of 0, ev_stride not 4 or 5, a null pointer.  Asynchronous on `stream`, allocates nothing, capturable. */
+int ev2h_events_undistort(double* events, int ev_stride, int n_rows, const double* camera_matrix, const double* dist, int n_dist,
+                          int width, int height, int32_t* first_bad, ev2h_stream_t stream);
+
 /* ---- recording -> evaluation windows (dataset/evaluation_stream.py:53-146,177-184; dataset/ev2hands_r.py:96-99) ------------ */
 /* A recording is n_rows (< 2^31: row indices are 32-bit) device float64 rows of ev_stride (>= 4) columns (x, y, t_us, polarity[,
  * frame index]) in stream order with NON-DECREASING timestamps.  t_ms(i) = t_us[i] * 1e-3 rounded once (get_event, :102);

@@ -1,7 +1,7 @@
 """Validate the MI355X path on the REAL assets (licensed MANO_{LEFT,RIGHT}.pkl + best_model_state_dict.pth), which this
 repository cannot ship and its CI has never seen.
 
-Two steps, on two machines:
+Two steps, on two machines (and an optional third):
 
   1. where the reference runs (its conda env with manopth; CPU is enough):
 
@@ -21,6 +21,14 @@ Two steps, on two machines:
      loads the pkl files with the chumpy-free reader (ev2hands_amd/mano.py), the checkpoint with the drop-in wrapper, replays the
      recorded inputs through libev2hands_hip.so and reports max relative error per output, segmentation argmax agreement and the
      root-relative MPJPE (mm, evaluate_ev2hands_r.py:43-54) against the reference -- in every arithmetic mode.
+
+  3. optional, where `cv2` is importable and one of the reference's real recordings (a `.pickle`) is at hand, on the MI355X box:
+
+       python tools/validate_real_assets.py undistort --pickle /path/to/recording.pickle
+
+     undistorts the recording's events with `EventStream.from_raw` and with `camera.undistort`'s arithmetic through `cv2`
+     (src/camera.py:157-168: cv2.undistortPoints on the float32 pixels, `@ mtx.T`, the clip) and prints the largest difference.
+     The library restates cv2.undistortPoints from public OpenCV 4.x and no test here can hold it to cv2 itself: this leg can.
 
 `python tests/real_assets_dryrun.py DIR OUT` replaces the reference by this repository's CPU oracle and a synthetic checkpoint /
 MANO-shaped assets written in the real file formats: a dry run of the whole procedure (tests/test_real_assets.py uses it; the oracle
@@ -189,6 +197,37 @@ def cmd_check(a) -> int:
     return 0 if ok else 1
 
 
+# ------------------------------------------------------------------------------------------------ undistort
+def cmd_undistort(a) -> int:
+    """EventStream.from_raw against camera.undistort's arithmetic through cv2, on a real recording.  A tool leg, not a test: it
+    needs cv2 and a file this repository cannot ship."""
+    try:
+        import cv2
+    except ImportError:
+        print("cv2 is not importable here: the cross-check needs it (nothing was compared)")
+        return 2
+    from ev2hands_amd.events import OUTPUT_HEIGHT, OUTPUT_WIDTH
+    from ev2hands_amd.stream import EventStream
+    with open(a.pickle, "rb") as f:
+        data = pickle.load(f)
+    events, cam = np.asarray(data["events"]), data["camera"]
+    if a.max_events:
+        events = events[:a.max_events]
+    mtx, dist = np.asarray(cam["camera_matrix"], dtype=np.float64), np.asarray(cam["dist"], dtype=np.float64)
+    # camera.py:157-168 on evaluation_stream.py:40's argument
+    und = cv2.undistortPoints(events[:, :2][:, None, ...].astype(np.float32), mtx, dist).reshape(-1, 2)
+    und = (np.c_[und, np.ones_like(und[:, 0])] @ mtx.T)[:, :2]
+    und[:, 0] = np.clip(und[:, 0], 0, OUTPUT_WIDTH - 1)
+    und[:, 1] = np.clip(und[:, 1], 0, OUTPUT_HEIGHT - 1)
+    got = EventStream.from_raw(a.device, events, mtx, dist).events[:, :2].cpu().numpy()
+    diff = np.abs(got - und.astype(np.float64))
+    row = int(np.argmax(diff.max(1)))
+    other_pixel = int((np.trunc(got) != np.trunc(und)).any(1).sum())
+    print(f"{events.shape[0]} events, {dist.size} distortion coefficients, cv2 {cv2.__version__}: largest |from_raw - cv2| {diff.max():.3e} px "
+          f"(row {row}: {got[row].tolist()} vs {und[row].tolist()}); rows whose truncated pixel differs: {other_pixel}")
+    return 0
+
+
 def main() -> int:
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     sub = ap.add_subparsers(dest="cmd", required=True)
@@ -201,7 +240,13 @@ def main() -> int:
     c.add_argument("--fixture", required=True)
     c.add_argument("--mano", required=True)
     c.add_argument("--ckpt", required=True)
+    u = sub.add_parser("undistort")
+    u.add_argument("--pickle", required=True, help="one of the reference's real recordings (evaluation_stream.py:32-38)")
+    u.add_argument("--device", default="cuda:0")
+    u.add_argument("--max-events", type=int, default=0, help="compare the first N events only")
     a = ap.parse_args()
+    if a.cmd == "undistort":
+        return cmd_undistort(a)
     if a.cmd == "make":
         if not (a.reference and a.mano and a.ckpt):
             ap.error("make needs --reference, --mano and --ckpt (a dry run with synthetic assets: python tests/real_assets_dryrun.py DIR OUT)")
