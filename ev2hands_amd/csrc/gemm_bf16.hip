@@ -1,22 +1,35 @@
 // Dense layers on the 16-bit matrix pipe: same contract as gemm.hip (ev2h_gemm), operands split on the fly into the
 // NS planes of planes.hpp (NS = 2 "f16x2", NS = 3 "bf16x3": fp32-class; NS = 1 plain bf16; NS = 4 [r6] the mode code of "f16": ONE
 // fp16 plane with f16x2's range scaling -- plane_count(NS) planes are stored, planes_f16(NS) selects the scaling), fp32 accumulate.
-// Three kernels: a generic one that splits both operands (W without a plane image: the tiny heads), a wide 128x256
-// one and the default 128x128 "occupancy" kernel, both with host-packed W plane images streamed by LDS-DMA.
-// First kernel:
-// 128x128x32 tiles, 8 waves (2 x 4), each wave 64 x 32 outputs (2 accumulator tiles); LDS rows hold the
-// NS planes side by side (NS*64 B + 16 B pad => conflict-free ds_read_b128); register prefetch of the
-// next K tile, two LDS buffers, one barrier per K tile.
+// Four kernel templates, all on 32-wide K tiles whose LDS rows hold a row's planes side by side (GemmTile):
+//   gemm_nt_bf16_kernel<NS, GEN>              generic: splits BOTH operands (W without a plane image: the tiny heads; GEN: range groups
+//                                             that do not tile by 128 rows), 128 x 128 tiles, 8 waves
+//   gemm_nt_bf16_wide_kernel<NS>              128 x 256 tiles, 8 waves, 256-row W plane images
+//   gemm_nt_bf16_occ_kernel<NS,TAP3,PIPE,ZS>  the default: 128 x 128 tiles, 4 waves, three workgroups per CU, 128-row W plane images; TAP3 = the
+//                                             k = 3 convolution with one split per channel chunk, PIPE = two buffers for grids smaller than the
+//                                             chip, ZS = the attention's key-weighted sums as the epilogue (zsum_epilogue)
+//   gemm_nt_bf16_small_kernel<NS>             64 x 64 tiles of the same 128-row images for the smallest grids
+// The image kernels stream host-packed W plane images (csrc/pack.hip: gemm_image) by LDS-DMA and split only X.  Every kernel is its own
+// K-loop schedule (who loads when, which barrier where) over the SAME steps, each written once below: the operand row's address
+// (x_operand), its split into LDS (planes.hpp: store_planes8), the W tile's DMA (dma_tile), one K tile of MFMAs (mma_k32) and the
+// epilogues' column constants and range scales (col_affine, x_group_amax) -- so all of them sum the same products in the same order.
 #include <cstdlib>
+#include <type_traits>
 
 #include "planes.hpp"
 #include "ev2hands_hip.h"
 
 namespace {
 
-
+// tiles: rows and K step of every kernel but the small one; columns of the generic (GB), wide (GW) and occupancy (GO) kernels
 constexpr int GB_BM = 128, GB_BN = 128, GB_BK = 32, GB_THREADS = 512;
-constexpr int GO_THREADS_ = 256, GB_BN_ = 128;      // (occupancy kernel: threads, tile columns -- used by zsum_epilogue above its definition)
+constexpr int GW_BN = 256;
+constexpr int GO_BN = 128, GO_THREADS = 256;
+
+template <int NS>
+struct GemmTile {
+    static constexpr int RS = plane_count(NS) * 64 + 16;      // bytes per LDS row: planes of 32 16-bit values + 16 B pad => conflict-free ds_read_b128
+};
 
 struct GemmBP {
     const float* X; int ldx;
@@ -42,35 +55,102 @@ struct GemmBP {
     const float* x_scale;   // NS = 4 with x_bf16 [r6]: the power of two each group's fp16 rows were stored with (float [groups]); replaces x_amax
 };
 
-template <int NS>
-struct GBCfg {
-    static constexpr int RS = plane_count(NS) * 64 + 16;      // bytes per LDS row (planes of 32 16-bit values + pad)
-    static constexpr int OPER = GB_BM * RS;                 // one operand tile
-    static constexpr int LDS_BYTES = 4 * OPER;              // 2 buffers x (A, B)
-};
-
-
+// ------------------------------------------------------------------------------------------ the steps the kernels share
+// range group of X row m (rows outside the matrix take the nearest one's), and the maximum its one or two records hold
+__device__ __forceinline__ long x_group(const GemmBP& p, long m) { return (m < 0 ? 0 : (m < p.M ? m : p.M - 1)) / p.x_group_rows; }
+__device__ __forceinline__ unsigned x_group_amax(const GemmBP& p, long m) {
+    const long g = x_group(p, m);
+    unsigned a = p.x_amax[g];
+    if (p.x_amax2) a = max(a, p.x_amax2[g]);
+    return a;
+}
 // power-of-two scale of X row m (f16x2 with a range record, 1 otherwise)
 template <int NS>
 __device__ __forceinline__ float x_row_scale(const GemmBP& p, long m) {
     if constexpr (!planes_f16(NS)) return 1.f;
-    if (p.x_scale) {                         // fp16 rows stored scaled: that power of two IS the operand's scale
-        const long mm = m < 0 ? 0 : (m < p.M ? m : p.M - 1);
-        return p.x_scale[mm / p.x_group_rows];
-    }
+    if (p.x_scale) return p.x_scale[x_group(p, m)];      // fp16 rows stored scaled: that power of two IS the operand's scale
     if (!p.x_amax) return 1.f;
-    const long mm = m < 0 ? 0 : (m < p.M ? m : p.M - 1);
-    const long g = mm / p.x_group_rows;
-    unsigned a = p.x_amax[g];
-    if (p.x_amax2) a = max(a, p.x_amax2[g]);
-    return f16x2_scale(a);
+    return f16x2_scale(x_group_amax(p, m));
 }
 template <int NS>
 __device__ __forceinline__ void scale_rows(f32x4& v, float s) {
     if constexpr (planes_f16(NS)) v *= s;       // exact (power of two); the products are multiplied back in the epilogue
 }
 
-// Epilogue shared by the three kernels.  acc[i][j][r] = output (row m0 + row0 + 32 i + mfma_row(r, half), column col0 + 32 j + l31):
+// Row m, column k of the virtual [M][taps * Kc] operand (taps == 3: [x(m - 1) | x(m) | x(m + 1)], zero outside m's sequence): where its
+// 8 / 16-float segment starts in X, and whether it exists (`ok` false: a valid address whose values the caller zero-fills)
+__device__ __forceinline__ const float* x_operand(const GemmBP& p, int m, int k, bool& ok) {
+    ok = (m < p.M) && (k < p.K);
+    long src = m;
+    int kc = k;
+    if (p.taps == 3) {
+        const int tap = k / p.Kc;
+        kc = k - tap * p.Kc;
+        const int pos = m % p.rows_per_seq + tap - 1;
+        ok = ok && (pos >= 0) && (pos < p.rows_per_seq);
+        src = (long)m + tap - 1;
+    }
+    return p.X + (ok ? src : 0) * p.ldx + (ok ? kc : 0);
+}
+
+// One tile image of BYTES bytes from global memory straight into LDS, in 1 KiB pieces (64 lanes x 16 B) dealt round to WAVES waves
+template <int BYTES, int WAVES>
+__device__ __forceinline__ void dma_tile(const char* src, char* dst, int wave, int lane) {
+    static_assert(BYTES % 1024 == 0, "a tile image must be a whole number of 1 KiB DMA pieces");
+    for (int off = wave * 1024; off < BYTES; off += WAVES * 1024)
+        __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(src + off + lane * 16),
+                                         (__attribute__((address_space(3))) void*)(dst + off), 16, 0, 0);
+}
+
+template <int NI, int NJ>
+__device__ __forceinline__ void zero_acc(f32x16 (&acc)[NI][NJ]) {
+#pragma unroll
+    for (int i = 0; i < NI; ++i)
+#pragma unroll
+        for (int j = 0; j < NJ; ++j)
+#pragma unroll
+            for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
+}
+
+// One 32-wide K tile of a wave's NI x NJ accumulator tiles (32 x 32 each): pa / pb = this lane's row of the first A / B fragment in
+// tiles of RS-byte rows; the next fragment is 32 rows on.  Per 16-column k block: all fragment reads, then the MFMAs plane-product
+// outer, accumulator inner -- consecutive MFMAs never depend on each other, and every accumulator sums its products in one order.
+template <int NS, int NI, int NJ, int RS>
+__device__ __forceinline__ void mma_k32(const char* pa, const char* pb, f32x16 (&acc)[NI][NJ]) {
+#pragma unroll
+    for (int m = 0; m < 2; ++m) {
+        u32x4 a[NI][plane_count(NS)], b[NJ][plane_count(NS)];
+#pragma unroll
+        for (int s = 0; s < plane_count(NS); ++s) {
+#pragma unroll
+            for (int i = 0; i < NI; ++i) a[i][s] = *reinterpret_cast<const u32x4*>(pa + i * 32 * RS + s * 64 + m * 32);
+#pragma unroll
+            for (int j = 0; j < NJ; ++j) b[j][s] = *reinterpret_cast<const u32x4*>(pb + j * 32 * RS + s * 64 + m * 32);
+        }
+#pragma unroll
+        for (int q = 0; q < Planes<NS>::NPROD; ++q)
+#pragma unroll
+            for (int i = 0; i < NI; ++i)
+#pragma unroll
+                for (int j = 0; j < NJ; ++j)
+                    acc[i][j] = mfma_planes<NS>(a[i][Planes<NS>::A[q]], b[j][Planes<NS>::B[q]], acc[i][j]);
+    }
+}
+
+// bias, post scale and post shift of the NJ columns col0 + 32 j + l31 of a lane (0 / 1 / 0 where absent or past N)
+template <int NJ>
+__device__ __forceinline__ void col_affine(const GemmBP& p, const float* bias, int col0, int l31, float (&bj)[NJ], float (&sj)[NJ], float (&tj)[NJ]) {
+#pragma unroll
+    for (int j = 0; j < NJ; ++j) {
+        const int col = col0 + j * 32 + l31;
+        const bool okc = col < p.N;
+        bj[j] = (bias && okc) ? bias[col] : 0.f;
+        sj[j] = (p.post_scale && okc) ? p.post_scale[col] : 1.f;
+        tj[j] = (p.post_shift && okc) ? p.post_shift[col] : 0.f;
+    }
+}
+
+// Epilogue shared by the four kernels.  acc[i][j][r] = output (row m0 + row0 + 32 i + mfma_row(r, half), column col0 + 32 j + l31):
 //   v = acc * (w_unscale / x_scale(row)) + bias;  ReLU;  post affine;  [* y_scale];  store, or max over the tile's 128 rows;
 //   optional atomicMax of |v| into the output's range record.
 // GEN = false (the two fast kernels, and the generic one on aligned shapes): every 128-row tile lies inside one range group, so
@@ -83,23 +163,12 @@ __device__ __forceinline__ void gemm_epilogue(const GemmBP& p, f32x16 (&acc)[NI]
     const float* bias = p.bias;
     if (bias && p.bias_group_rows > 0) bias += (long)(m0 / p.bias_group_rows) * p.ldbias;
     float bj[NJ], sj[NJ], tj[NJ];
-#pragma unroll
-    for (int j = 0; j < NJ; ++j) {
-        const int col = col0 + j * 32 + l31;
-        const bool okc = col < p.N;
-        bj[j] = (bias && okc) ? bias[col] : 0.f;
-        sj[j] = (p.post_scale && okc) ? p.post_scale[col] : 1.f;
-        tj[j] = (p.post_shift && okc) ? p.post_shift[col] : 0.f;
-    }
+    col_affine<NJ>(p, bias, col0, l31, bj, sj, tj);
     const bool xs_on = planes_f16(NS) && p.x_amax != nullptr;
     const bool ys_on = planes_f16(NS) && p.y_scale != nullptr;
     const bool track = planes_f16(NS) && p.y_amax != nullptr;
     auto y_store_scale = [&](long row) {          // power of two that keeps y_bound_w * max|X_g| + y_bound_b below 2^15
-        const long rr = row < p.M ? row : p.M - 1;
-        const long g = rr / p.x_group_rows;
-        unsigned a = p.x_amax[g];
-        if (p.x_amax2) a = max(a, p.x_amax2[g]);
-        return f16x2_scale(__float_as_uint(__fmaf_rn(p.y_bound_w, __uint_as_float(a), p.y_bound_b)));
+        return f16x2_scale(__float_as_uint(__fmaf_rn(p.y_bound_w, __uint_as_float(x_group_amax(p, row)), p.y_bound_b)));
     };
     float cx_u = p.w_unscale;
     float sy_u = 1.f;
@@ -191,10 +260,19 @@ __device__ __forceinline__ void gemm_epilogue(const GemmBP& p, f32x16 (&acc)[NI]
     }
 }
 
+// ---------------------------------------------------------------------------------------- generic: both operands split on the fly
+// 128 x 128 x 32 tiles, 8 waves (2 x 4), each wave 64 x 32 outputs (2 accumulator tiles); register prefetch of the next K tile, two
+// LDS buffers, one barrier per K tile.
+template <int NS>
+struct GBCfg {
+    static constexpr int OPER = GB_BM * GemmTile<NS>::RS;   // one operand tile
+    static constexpr int LDS_BYTES = 4 * OPER;              // 2 buffers x (A, B)
+};
+
 template <int NS, bool GEN>
 __global__ __launch_bounds__(GB_THREADS, 2) void gemm_nt_bf16_kernel(GemmBP p) {
     using Cfg = GBCfg<NS>;
-    constexpr int RS = Cfg::RS;
+    constexpr int RS = GemmTile<NS>::RS;
     const float w_prescale = 1.f / p.w_unscale;
     extern __shared__ __attribute__((aligned(16))) char smem[];
     char* sA0 = smem;
@@ -216,20 +294,9 @@ __global__ __launch_bounds__(GB_THREADS, 2) void gemm_nt_bf16_kernel(GemmBP p) {
 
     auto gload = [&](int kt) {
         const int k = kt * GB_BK + lseg * 8;
-        int tap = 0, kc = k;
-        if (p.taps == 3) { tap = k / p.Kc; kc = k - tap * p.Kc; }
         {
-            const int m = m0 + lrow;
-            bool ok = (m < p.M) && (k < p.K);
-            long src = m;
-            if (p.taps == 3) {
-                const int pos = m % p.rows_per_seq + tap - 1;
-                ok = ok && (pos >= 0) && (pos < p.rows_per_seq);
-                src = (long)m + tap - 1;
-            }
-            const long mm = ok ? src : 0;
-            const int kk = ok ? kc : 0;
-            const f32x4* g = reinterpret_cast<const f32x4*>(p.X + mm * p.ldx + kk);
+            bool ok;
+            const f32x4* g = reinterpret_cast<const f32x4*>(x_operand(p, m0 + lrow, k, ok));
             f32x4 v0 = g[0], v1 = g[1];
             if (!ok) { v0 = f32x4{0.f, 0.f, 0.f, 0.f}; v1 = v0; }
             scale_rows<NS>(v0, xs); scale_rows<NS>(v1, xs);
@@ -244,24 +311,10 @@ __global__ __launch_bounds__(GB_THREADS, 2) void gemm_nt_bf16_kernel(GemmBP p) {
             rb[0] = v0 * w_prescale; rb[1] = v1 * w_prescale;       // exact (power of two)
         }
     };
-    auto swrite_one = [&](char* dst, const f32x4 (&r)[2]) {
-        unsigned q[4][plane_count(NS)];
-        split_planes<NS>(r[0][0], r[0][1], q[0]);
-        split_planes<NS>(r[0][2], r[0][3], q[1]);
-        split_planes<NS>(r[1][0], r[1][1], q[2]);
-        split_planes<NS>(r[1][2], r[1][3], q[3]);
-#pragma unroll
-        for (int s = 0; s < plane_count(NS); ++s) {
-            u32x4 v = {q[0][s], q[1][s], q[2][s], q[3][s]};
-            *reinterpret_cast<u32x4*>(dst + lrow * RS + s * 64 + lseg * 16) = v;
-        }
-    };
+    auto swrite_one = [&](char* dst, const f32x4 (&r)[2]) { store_planes8<NS>(dst + lrow * RS + lseg * 16, r[0], r[1]); };
 
     f32x16 acc[2][1];
-#pragma unroll
-    for (int i = 0; i < 2; ++i)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) acc[i][0][r] = 0.f;
+    zero_acc(acc);
 
     const int nk = (p.K + GB_BK - 1) / GB_BK;
     gload(0);
@@ -274,21 +327,7 @@ __global__ __launch_bounds__(GB_THREADS, 2) void gemm_nt_bf16_kernel(GemmBP p) {
         if (kt + 1 < nk) gload(kt + 1);
         const char* pa = sA + (wm * 64 + l31) * RS + half * 16;
         const char* pb = sB + (wn * 32 + l31) * RS + half * 16;
-#pragma unroll
-        for (int m = 0; m < 2; ++m) {
-            u32x4 b[plane_count(NS)], a0[plane_count(NS)], a1[plane_count(NS)];
-#pragma unroll
-            for (int s = 0; s < plane_count(NS); ++s) {
-                b[s] = *reinterpret_cast<const u32x4*>(pb + s * 64 + m * 32);
-                a0[s] = *reinterpret_cast<const u32x4*>(pa + s * 64 + m * 32);
-                a1[s] = *reinterpret_cast<const u32x4*>(pa + 32 * RS + s * 64 + m * 32);
-            }
-#pragma unroll
-            for (int q = 0; q < Planes<NS>::NPROD; ++q) {
-                acc[0][0] = mfma_planes<NS>(a0[Planes<NS>::A[q]], b[Planes<NS>::B[q]], acc[0][0]);
-                acc[1][0] = mfma_planes<NS>(a1[Planes<NS>::A[q]], b[Planes<NS>::B[q]], acc[1][0]);
-            }
-        }
+        mma_k32<NS, 2, 1, RS>(pa, pb, acc);
         if (kt + 1 < nk) {
             swrite_one((kt & 1) ? sA0 : sA1, ra);
             swrite_one((kt & 1) ? sB0 : sB1, rb);
@@ -298,35 +337,21 @@ __global__ __launch_bounds__(GB_THREADS, 2) void gemm_nt_bf16_kernel(GemmBP p) {
     gemm_epilogue<NS, 2, 1, GEN>(p, acc, m0, wm * 64, n0 + wn * 32, wm, wn * 32, GB_BN, reinterpret_cast<float*>(smem), tid);
 }
 
-template <int NS, bool GEN>
-int launch_gb(const GemmBP& p, hipStream_t st) {
-    static PerDevice attr_set{};
-    EV2H_ONCE_PER_DEVICE(attr_set,
-        EV2H_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_nt_bf16_kernel<NS, GEN>),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, GBCfg<NS>::LDS_BYTES)););
-    gemm_nt_bf16_kernel<NS, GEN><<<p.nblk, GB_THREADS, GBCfg<NS>::LDS_BYTES, st>>>(p);
-    EV2H_CHECK_LAUNCH();
-    return EV2H_OK;
-}
-
 // ---------------------------------------------------------------------------------------- wide tile, pre-split W
 // 128 x 256 x 32 tiles for the big layers (N >= 192): W arrives as host-packed bf16 plane images of the LDS
 // tile (csrc/pack.hip: gemm_image) and is streamed by LDS-DMA; only X is split on the fly.
 // 8 waves as 2 x 4, each wave 64 x 64 = 2 x 2 accumulator tiles: 12 fragment reads feed 24 MFMAs.
-constexpr int GW_BN = 256;
-
 template <int NS>
 struct GWCfg {
-    static constexpr int RS = plane_count(NS) * 64 + 16;
-    static constexpr int A_BYTES = GB_BM * RS;
-    static constexpr int B_BYTES = GW_BN * RS;
+    static constexpr int A_BYTES = GB_BM * GemmTile<NS>::RS;
+    static constexpr int B_BYTES = GW_BN * GemmTile<NS>::RS;
     static constexpr int LDS_BYTES = 2 * (A_BYTES + B_BYTES);
 };
 
 template <int NS>
 __global__ __launch_bounds__(GB_THREADS, 2) void gemm_nt_bf16_wide_kernel(GemmBP p, const char* __restrict__ Ws) {
     using Cfg = GWCfg<NS>;
-    constexpr int RS = Cfg::RS;
+    constexpr int RS = GemmTile<NS>::RS;
     extern __shared__ __attribute__((aligned(16))) char smem[];
     char* sA0 = smem;
     char* sA1 = smem + Cfg::A_BYTES;
@@ -347,55 +372,23 @@ __global__ __launch_bounds__(GB_THREADS, 2) void gemm_nt_bf16_wide_kernel(GemmBP
     const float xs = x_row_scale<NS>(p, m0);          // one range group per tile (ev2h_gemm_bf16 sends other shapes to the generic kernel)
 
     auto gload = [&](int kt) {
-        const int k = kt * GB_BK + lseg * 8;
-        int tap = 0, kc = k;
-        if (p.taps == 3) { tap = k / p.Kc; kc = k - tap * p.Kc; }
-        const int m = m0 + lrow;
-        bool ok = (m < p.M) && (k < p.K);
-        long src = m;
-        if (p.taps == 3) {
-            const int pos = m % p.rows_per_seq + tap - 1;
-            ok = ok && (pos >= 0) && (pos < p.rows_per_seq);
-            src = (long)m + tap - 1;
-        }
-        const float* g = p.X + (ok ? src : 0) * p.ldx + (ok ? kc : 0);
+        const float* g = x_operand(p, m0 + lrow, kt * GB_BK + lseg * 8, oka);
         // Issued from inline asm: once an LDS-DMA is in flight hipcc waits vmcnt(0) at (and before) every ordinary
         // load it tracks, which would make the DMA synchronous.  These loads are waited for by hand (wait_all).
         asm volatile("global_load_dwordx4 %0, %2, off\n\tglobal_load_dwordx4 %1, %2, off offset:16"
                      : "=&v"(ra[0]), "=&v"(ra[1]) : "v"(g) : "memory");
-        oka = ok;
     };
     auto wait_all = [&]() { asm volatile("s_waitcnt vmcnt(0)" : "+v"(ra[0]), "+v"(ra[1]) : : "memory"); };
     auto swrite = [&](char* dst) {
         f32x4 r[2] = {ra[0], ra[1]};
         if (!oka) { r[0] = f32x4{0.f, 0.f, 0.f, 0.f}; r[1] = r[0]; }
         scale_rows<NS>(r[0], xs); scale_rows<NS>(r[1], xs);
-        unsigned q[4][plane_count(NS)];
-        split_planes<NS>(r[0][0], r[0][1], q[0]);
-        split_planes<NS>(r[0][2], r[0][3], q[1]);
-        split_planes<NS>(r[1][0], r[1][1], q[2]);
-        split_planes<NS>(r[1][2], r[1][3], q[3]);
-#pragma unroll
-        for (int s = 0; s < plane_count(NS); ++s) {
-            u32x4 v = {q[0][s], q[1][s], q[2][s], q[3][s]};
-            *reinterpret_cast<u32x4*>(dst + lrow * RS + s * 64 + lseg * 16) = v;
-        }
+        store_planes8<NS>(dst + lrow * RS + lseg * 16, r[0], r[1]);
     };
-    auto dma_b = [&](int kt, char* dst) {
-        const char* src = Ws + ((size_t)tn * nk + kt) * Cfg::B_BYTES;
-        for (int off = wave * 1024; off < Cfg::B_BYTES; off += 8 * 1024)
-            __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(src + off + lane * 16),
-                                             (__attribute__((address_space(3))) void*)(dst + off), 16, 0, 0);
-    };
-    static_assert(Cfg::B_BYTES % 1024 == 0, "B tile image must be a whole number of 1 KiB DMA pieces");
+    auto dma_b = [&](int kt, char* dst) { dma_tile<Cfg::B_BYTES, 8>(Ws + ((size_t)tn * nk + kt) * Cfg::B_BYTES, dst, wave, lane); };
 
     f32x16 acc[2][2];
-#pragma unroll
-    for (int i = 0; i < 2; ++i)
-#pragma unroll
-        for (int j = 0; j < 2; ++j)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
+    zero_acc(acc);
 
     dma_b(0, sB0);
     gload(0);
@@ -413,27 +406,9 @@ __global__ __launch_bounds__(GB_THREADS, 2) void gemm_nt_bf16_wide_kernel(GemmBP
         }
         const char* pa = sA + (wm * 64 + l31) * RS + half * 16;
         const char* pb = sB + (wn * 64 + l31) * RS + half * 16;
-#pragma unroll
-        for (int m = 0; m < 2; ++m) {
-            u32x4 a[2][plane_count(NS)], b[2][plane_count(NS)];
-#pragma unroll
-            for (int s = 0; s < plane_count(NS); ++s) {
-                a[0][s] = *reinterpret_cast<const u32x4*>(pa + s * 64 + m * 32);
-                a[1][s] = *reinterpret_cast<const u32x4*>(pa + 32 * RS + s * 64 + m * 32);
-                b[0][s] = *reinterpret_cast<const u32x4*>(pb + s * 64 + m * 32);
-                b[1][s] = *reinterpret_cast<const u32x4*>(pb + 32 * RS + s * 64 + m * 32);
-            }
-            // plane-product outer, accumulator inner: consecutive MFMAs never depend on each other
-#pragma unroll
-            for (int q = 0; q < Planes<NS>::NPROD; ++q)
-#pragma unroll
-                for (int i = 0; i < 2; ++i)
-#pragma unroll
-                    for (int j = 0; j < 2; ++j)
-                        acc[i][j] = mfma_planes<NS>(a[i][Planes<NS>::A[q]], b[j][Planes<NS>::B[q]], acc[i][j]);
-        }
+        mma_k32<NS, 2, 2, RS>(pa, pb, acc);
         if (more) {
-            wait_all();                 // X rows (and, being older, the DMA pieces of this wave) have landed
+            wait_all();                // X rows (and, being older, the DMA pieces of this wave) have landed
             swrite((kt & 1) ? sA0 : sA1);
         }
         __builtin_amdgcn_s_waitcnt(0x0070);     // vmcnt(0) lgkmcnt(0)
@@ -441,17 +416,6 @@ __global__ __launch_bounds__(GB_THREADS, 2) void gemm_nt_bf16_wide_kernel(GemmBP
     }
 
     gemm_epilogue<NS, 2, 2, false>(p, acc, m0, wm * 64, n0 + wn * 64, wm, wn * 64, GW_BN, reinterpret_cast<float*>(smem), tid);
-}
-
-template <int NS>
-int launch_gw(const GemmBP& p, const char* Ws, hipStream_t st) {
-    static PerDevice attr_set{};
-    EV2H_ONCE_PER_DEVICE(attr_set,
-        EV2H_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_nt_bf16_wide_kernel<NS>),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, GWCfg<NS>::LDS_BYTES)););
-    gemm_nt_bf16_wide_kernel<NS><<<p.nblk, GB_THREADS, GWCfg<NS>::LDS_BYTES, st>>>(p, Ws);
-    EV2H_CHECK_LAUNCH();
-    return EV2H_OK;
 }
 
 // ---------------------------------------------------------------------------------------- q1 never written
@@ -473,7 +437,7 @@ __device__ __forceinline__ void zsum_epilogue(const GemmBP& p, f32x16 (&acc)[2][
     float* red = keyL + 4 * KLD;                               // [12][128]: the partial of the lower 64 rows' waves
     __syncthreads();                                           // the operand tiles are dead
     const int pos0 = m0 % p.rows_per_seq;
-    for (int i = tid; i < GB_BM + 2; i += GO_THREADS_) {
+    for (int i = tid; i < GB_BM + 2; i += GO_THREADS) {
         const int pos = pos0 - 1 + i;
         const long row = (long)m0 - 1 + i;
         float4 k = make_float4(0.f, 0.f, 0.f, 0.f);
@@ -481,16 +445,8 @@ __device__ __forceinline__ void zsum_epilogue(const GemmBP& p, f32x16 (&acc)[2][
         keyL[i] = k.x; keyL[KLD + i] = k.y; keyL[2 * KLD + i] = k.z; keyL[3 * KLD + i] = k.w;
     }
     // q1 values of this wave: bias, ReLU, BN affine -- the store epilogue's arithmetic
-    const float* bias = p.bias;
     float bj[2], sj[2], tj[2];
-#pragma unroll
-    for (int j = 0; j < 2; ++j) {
-        const int col = n0 + wn * 64 + j * 32 + l31;
-        const bool okc = col < p.N;
-        bj[j] = (bias && okc) ? bias[col] : 0.f;
-        sj[j] = (p.post_scale && okc) ? p.post_scale[col] : 1.f;
-        tj[j] = (p.post_shift && okc) ? p.post_shift[col] : 0.f;
-    }
+    col_affine<2>(p, p.bias, n0 + wn * 64, l31, bj, sj, tj);
     float cx = p.w_unscale;
     if (planes_f16(NS) && (p.x_amax || p.x_scale)) cx = p.w_unscale * pow2_inverse(x_row_scale<NS>(p, m0));
     float amf = 0.f;
@@ -563,7 +519,7 @@ __device__ __forceinline__ void zsum_epilogue(const GemmBP& p, f32x16 (&acc)[2][
 #pragma unroll
             for (int r = 0; r < 8; ++r) {
                 const int mr = mfma_row(r, half);
-                if (mr < 12) red[mr * GB_BN_ + wn * 64 + j * 32 + l31] = (z[j][r] * iq) * ik;
+                if (mr < 12) red[mr * GO_BN + wn * 64 + j * 32 + l31] = (z[j][r] * iq) * ik;
             }
     }
     __syncthreads();
@@ -574,7 +530,7 @@ __device__ __forceinline__ void zsum_epilogue(const GemmBP& p, f32x16 (&acc)[2][
             for (int r = 0; r < 8; ++r) {
                 const int mr = mfma_row(r, half);
                 const int col = n0 + wn * 64 + j * 32 + l31;
-                if (mr < 12 && col < p.N) zp[(size_t)mr * p.N + col] = (z[j][r] * iq) * ik + red[mr * GB_BN_ + wn * 64 + j * 32 + l31];
+                if (mr < 12 && col < p.N) zp[(size_t)mr * p.N + col] = (z[j][r] * iq) * ik + red[mr * GO_BN + wn * 64 + j * 32 + l31];
             }
     }
 }
@@ -584,17 +540,15 @@ __device__ __forceinline__ void zsum_epilogue(const GemmBP& p, f32x16 (&acc)[2][
 // independent workgroups share a CU: while one sits at its barrier or stages the next K tile, the other two
 // keep the matrix pipe busy (the barrier/refill bubble of a lone 8-wave workgroup costs 12-20 % here, see
 // tools/ubench/mfma_lds.hip).  W arrives as 128-row plane images by LDS-DMA, X is split on the fly.
-constexpr int GO_BN = 128, GO_THREADS = 256;
-
+//
 // TAP3 (Conv1d k=3 along the rows, Kc % 32 == 0, rows_per_seq % 128 == 0): the three taps of one 32-wide channel chunk
 // are the same 130 rows of X shifted by one, so the chunk is loaded and split ONCE (128 rows + a one-row halo each side,
 // zero at the window ends) and the three W tiles of that chunk are multiplied against row-shifted views of it.
 template <int NS, bool TAP3>
 struct GOCfg {
-    static constexpr int RS = plane_count(NS) * 64 + 16;
     static constexpr int A_ROWS = GB_BM + (TAP3 ? 2 : 0);
-    static constexpr int A_BYTES = A_ROWS * RS;
-    static constexpr int B_BYTES = GO_BN * RS;
+    static constexpr int A_BYTES = A_ROWS * GemmTile<NS>::RS;
+    static constexpr int B_BYTES = GO_BN * GemmTile<NS>::RS;
     static constexpr int LDS_BYTES = A_BYTES + B_BYTES;
 };
 
@@ -609,7 +563,7 @@ template <int NS, bool TAP3, bool PIPE = false, bool ZS = false>
 __global__ __launch_bounds__(GO_THREADS, 3) void gemm_nt_bf16_occ_kernel(GemmBP p, const char* __restrict__ Ws) {
     static_assert(!ZS || TAP3, "the q1-free epilogue belongs to the tap kernel");
     using Cfg = GOCfg<NS, TAP3>;
-    constexpr int RS = Cfg::RS;
+    constexpr int RS = GemmTile<NS>::RS;
     static_assert(!(PIPE && TAP3), "the pipelined variant is for the plain K loop");
     extern __shared__ __attribute__((aligned(16))) char smem[];
     char* sA = smem;
@@ -629,7 +583,6 @@ __global__ __launch_bounds__(GO_THREADS, 3) void gemm_nt_bf16_occ_kernel(GemmBP 
     // one range group per tile (ev2h_gemm_bf16 sends other shapes to the generic kernel); the TAP3 halo rows m0 - 1 and
     // m0 + 128 lie in the tile's window whenever they are used, so they take the tile's scale too
     const float xs = x_row_scale<NS>(p, m0);
-    const float xsh = xs;
 
     // 16 consecutive floats of one X row.  K is a multiple of 8, not of 16: when only the first 8 lie inside the row (`full`
     // false) the second half is read from the first half's address -- never past the row -- and zeroed when the tile is
@@ -643,19 +596,8 @@ __global__ __launch_bounds__(GO_THREADS, 3) void gemm_nt_bf16_occ_kernel(GemmBP 
     };
     auto gload = [&](int kt, f32x4 (&dst)[4]) {
         const int k = kt * GB_BK + lseg * 16;
-        int tap = 0, kc = k;
-        if (p.taps == 3) { tap = k / p.Kc; kc = k - tap * p.Kc; }
-        const int m = m0 + lrow;
-        bool ok = (m < p.M) && (k < p.K);
-        long src = m;
-        if (p.taps == 3) {
-            const int pos = m % p.rows_per_seq + tap - 1;
-            ok = ok && (pos >= 0) && (pos < p.rows_per_seq);
-            src = (long)m + tap - 1;
-        }
         fulla = (k + 16 <= p.K);
-        load16(p.X + (ok ? src : 0) * p.ldx + (ok ? kc : 0), fulla, dst);
-        oka = ok;
+        load16(x_operand(p, m0 + lrow, k, oka), fulla, dst);
     };
     // TAP3: chunk kc of the centre rows (LDS rows 1..128) and, threads 0..3, of the two halo rows (LDS rows 0 and 129)
     // x_bf16 (NS = 1): 16 bf16 values = 32 bytes = the first two registers of ra / rh
@@ -699,56 +641,16 @@ __global__ __launch_bounds__(GO_THREADS, 3) void gemm_nt_bf16_occ_kernel(GemmBP 
             f32x4 r0 = r[2 * hh], r1 = r[2 * hh + 1];
             if (!ok || (hh == 1 && !fulla)) { r0 = f32x4{0.f, 0.f, 0.f, 0.f}; r1 = r0; }
             scale_rows<NS>(r0, sc); scale_rows<NS>(r1, sc);
-            unsigned q[4][plane_count(NS)];
-            split_planes<NS>(r0[0], r0[1], q[0]);
-            split_planes<NS>(r0[2], r0[3], q[1]);
-            split_planes<NS>(r1[0], r1[1], q[2]);
-            split_planes<NS>(r1[2], r1[3], q[3]);
-#pragma unroll
-            for (int s = 0; s < plane_count(NS); ++s) {
-                u32x4 v = {q[0][s], q[1][s], q[2][s], q[3][s]};
-                *reinterpret_cast<u32x4*>(sA + ldsrow * RS + s * 64 + lseg * 32 + hh * 16) = v;
-            }
+            store_planes8<NS>(sA + ldsrow * RS + lseg * 32 + hh * 16, r0, r1);
         }
     };
-    auto dma_b = [&](int kt) {
-        const char* src = Ws + ((size_t)tn * nk + kt) * Cfg::B_BYTES;
-        for (int off = wave * 1024; off < Cfg::B_BYTES; off += 4 * 1024)
-            __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(src + off + lane * 16),
-                                             (__attribute__((address_space(3))) void*)(sB + off), 16, 0, 0);
-    };
-    static_assert(Cfg::B_BYTES % 1024 == 0, "B tile image must be a whole number of 1 KiB DMA pieces");
+    auto dma_b = [&](int kt) { dma_tile<Cfg::B_BYTES, 4>(Ws + ((size_t)tn * nk + kt) * Cfg::B_BYTES, sB, wave, lane); };
 
     f32x16 acc[2][2];
-#pragma unroll
-    for (int i = 0; i < 2; ++i)
-#pragma unroll
-        for (int j = 0; j < 2; ++j)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
+    zero_acc(acc);
 
     auto mma_tile = [&](int arow) {
-        const char* pa = sA + (wm * 64 + l31 + arow) * RS + half * 16;
-        const char* pb = sB + (wn * 64 + l31) * RS + half * 16;
-#pragma unroll
-        for (int m = 0; m < 2; ++m) {
-            u32x4 a[2][plane_count(NS)], b[2][plane_count(NS)];
-#pragma unroll
-            for (int s = 0; s < plane_count(NS); ++s) {
-                a[0][s] = *reinterpret_cast<const u32x4*>(pa + s * 64 + m * 32);
-                a[1][s] = *reinterpret_cast<const u32x4*>(pa + 32 * RS + s * 64 + m * 32);
-                b[0][s] = *reinterpret_cast<const u32x4*>(pb + s * 64 + m * 32);
-                b[1][s] = *reinterpret_cast<const u32x4*>(pb + 32 * RS + s * 64 + m * 32);
-            }
-            // plane-product outer, accumulator inner: consecutive MFMAs never depend on each other
-#pragma unroll
-            for (int q = 0; q < Planes<NS>::NPROD; ++q)
-#pragma unroll
-                for (int i = 0; i < 2; ++i)
-#pragma unroll
-                    for (int j = 0; j < 2; ++j)
-                        acc[i][j] = mfma_planes<NS>(a[i][Planes<NS>::A[q]], b[j][Planes<NS>::B[q]], acc[i][j]);
-        }
+        mma_k32<NS, 2, 2, RS>(sA + (wm * 64 + l31 + arow) * RS + half * 16, sB + (wn * 64 + l31) * RS + half * 16, acc);
         __builtin_amdgcn_s_waitcnt(0x0070);              // all fragment reads returned before a tile is overwritten
     };
     if constexpr (TAP3) {
@@ -759,7 +661,7 @@ __global__ __launch_bounds__(GO_THREADS, 3) void gemm_nt_bf16_occ_kernel(GemmBP 
             gload3(kc);
             wait_all();
             swrite_row(ra, oka, lrow + 1, xs);
-            if (tid < 4) swrite_row(rh, okh, (tid >> 1) ? GB_BM + 1 : 0, xsh);
+            if (tid < 4) swrite_row(rh, okh, (tid >> 1) ? GB_BM + 1 : 0, xs);
             __builtin_amdgcn_s_waitcnt(0x0070);          // vmcnt(0) lgkmcnt(0)
             __builtin_amdgcn_s_barrier();
 #pragma unroll 1
@@ -774,50 +676,30 @@ __global__ __launch_bounds__(GO_THREADS, 3) void gemm_nt_bf16_occ_kernel(GemmBP 
             }
         }
     } else if constexpr (PIPE) {
-        // KT K-tiles (32 columns each) per step and buffer.  KT = 2 (to amortise the ~1.1 us issue-to-landing time of an LDS-DMA piece,
-        // MI355X_MICROARCH.md) measured the same as KT = 1 (B = 1 forward 1.166 vs 1.157 ms, K = 520 layer 32 us either way): with four
-        // waves on one CU a 128 x 128 x 32 tile step is bound by its own split + 24 MFMAs per wave (~1.2 us), not by the transport.
-        // KT = 1 keeps the footprint at 74 KB.  The tiles are multiplied in K order as in the single-buffer kernel.
-        constexpr int KT = 1;
-        char* const base = smem;
-        auto use = [&](int bufi, int j) { sA = base + (bufi * KT + j) * Cfg::LDS_BYTES; sB = sA + Cfg::A_BYTES; };
-        f32x4 rq[KT][4];
-        bool okq[KT], fullq[KT];
-        auto stage = [&](int kt0, int bufi) {            // request the tiles kt0 .. kt0 + KT - 1 (W by LDS-DMA, X into registers)
-#pragma unroll
-            for (int j = 0; j < KT; ++j)
-                if (kt0 + j < nk) {
-                    use(bufi, j);
-                    dma_b(kt0 + j);
-                    gload(kt0 + j, rq[j]);                // (straight into this tile's registers: they are valid only after commit's wait)
-                    okq[j] = oka; fullq[j] = fulla;
-                }
+        // Two buffers of one K tile each (74 KB); the tiles are multiplied in K order as in the single-buffer kernel.  (Two tiles per
+        // buffer measured the same: DESIGN_HISTORY.md.)  oka / fulla describe the tile in flight from its stage to its commit.
+        auto use = [&](int bufi) { sA = smem + bufi * Cfg::LDS_BYTES; sB = sA + Cfg::A_BYTES; };
+        auto stage = [&](int kt, int bufi) {             // request tile kt: W by LDS-DMA, X into registers (valid only after commit's wait)
+            use(bufi);
+            dma_b(kt);
+            gload(kt, ra);
         };
-        auto commit = [&](int kt0, int bufi) {           // the X rows have arrived: split them into the buffer
-            if constexpr (KT == 2)
-                asm volatile("s_waitcnt vmcnt(0)" : "+v"(rq[0][0]), "+v"(rq[0][1]), "+v"(rq[0][2]), "+v"(rq[0][3]), "+v"(rq[1][0]), "+v"(rq[1][1]), "+v"(rq[1][2]), "+v"(rq[1][3]) : : "memory");
-            else
-                asm volatile("s_waitcnt vmcnt(0)" : "+v"(rq[0][0]), "+v"(rq[0][1]), "+v"(rq[0][2]), "+v"(rq[0][3]) : : "memory");
-#pragma unroll
-            for (int j = 0; j < KT; ++j)
-                if (kt0 + j < nk) {
-                    use(bufi, j);
-                    fulla = fullq[j];
-                    swrite_row(rq[j], okq[j], lrow, xs);
-                }
+        auto commit = [&](int bufi) {                    // the X rows have arrived: split them into the buffer
+            wait_all();
+            use(bufi);
+            swrite_row(ra, oka, lrow, xs);
             __builtin_amdgcn_s_waitcnt(0x0070);          // vmcnt(0) lgkmcnt(0)
         };
         stage(0, 0);
-        commit(0, 0);
-        int bufi = 0;
-        for (int kt = 0; kt < nk; kt += KT, bufi ^= 1) {
+        commit(0);
+        for (int kt = 0; kt < nk; ++kt) {
+            const int bufi = kt & 1;
             __builtin_amdgcn_s_barrier();                // buffer `bufi` is complete; nobody reads the other one any more
-            const bool more = kt + KT < nk;
-            if (more) stage(kt + KT, bufi ^ 1);
-#pragma unroll
-            for (int j = 0; j < KT; ++j)
-                if (kt + j < nk) { use(bufi, j); mma_tile(0); }
-            if (more) commit(kt + KT, bufi ^ 1);
+            const bool more = kt + 1 < nk;
+            if (more) stage(kt + 1, bufi ^ 1);
+            use(bufi);
+            mma_tile(0);
+            if (more) commit(bufi ^ 1);
         }
         __builtin_amdgcn_s_barrier();                    // the epilogue reuses LDS (row-max reduction)
     } else {
@@ -840,17 +722,6 @@ __global__ __launch_bounds__(GO_THREADS, 3) void gemm_nt_bf16_occ_kernel(GemmBP 
     gemm_epilogue<NS, 2, 2, false>(p, acc, m0, wm * 64, n0 + wn * 64, wm, wn * 64, GO_BN, reinterpret_cast<float*>(smem), tid);
 }
 
-template <int NS, bool TAP3, bool ZS = false>
-int launch_go_t(const GemmBP& p, const char* Ws, hipStream_t st) {
-    static PerDevice attr_set{};
-    EV2H_ONCE_PER_DEVICE(attr_set,
-        EV2H_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_nt_bf16_occ_kernel<NS, TAP3, false, ZS>),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, GOCfg<NS, TAP3>::LDS_BYTES)););
-    gemm_nt_bf16_occ_kernel<NS, TAP3, false, ZS><<<p.nblk, GO_THREADS, GOCfg<NS, TAP3>::LDS_BYTES, st>>>(p, Ws);
-    EV2H_CHECK_LAUNCH();
-    return EV2H_OK;
-}
-
 // ---------------------------------------------------------------------------------------- small-grid variant
 // 64 x 64 x 32 tiles, 4 waves (2 x 2, each ONE 32 x 32 accumulator), two LDS buffers, for launches whose 128 x 128 tiling gives fewer
 // than 65 workgroups (one to a few windows at a time: the M = 128 B layers).  There a K step of the big tile -- the split of 128 rows
@@ -860,14 +731,13 @@ int launch_go_t(const GemmBP& p, const char* Ws, hipStream_t st) {
 // 16-column k blocks, the plane products): bit-identical, so the choice (by launch size) never shows in a result.
 template <int NS>
 struct GSCfg {
-    static constexpr int RS = plane_count(NS) * 64 + 16;
-    static constexpr int A_BYTES = 64 * RS, B_BYTES = 64 * RS, BUF = A_BYTES + B_BYTES, LDS_BYTES = 2 * BUF;
+    static constexpr int A_BYTES = 64 * GemmTile<NS>::RS, B_BYTES = 64 * GemmTile<NS>::RS, BUF = A_BYTES + B_BYTES, LDS_BYTES = 2 * BUF;
 };
 
 template <int NS>
 __global__ __launch_bounds__(GO_THREADS, 3) void gemm_nt_bf16_small_kernel(GemmBP p, const char* __restrict__ Ws) {
     using Cfg = GSCfg<NS>;
-    constexpr int RS = Cfg::RS;
+    constexpr int RS = GemmTile<NS>::RS;
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const int L = xcd_remap(blockIdx.x, p.nblk);
     const int tn = L % p.tiles_n, tm = L / p.tiles_n;
@@ -892,42 +762,16 @@ __global__ __launch_bounds__(GO_THREADS, 3) void gemm_nt_bf16_small_kernel(GemmB
         f32x4 a = r0, b = r1;
         if (!ok) { a = f32x4{0.f, 0.f, 0.f, 0.f}; b = a; }
         scale_rows<NS>(a, xs); scale_rows<NS>(b, xs);
-        unsigned q[4][plane_count(NS)];
-        split_planes<NS>(a[0], a[1], q[0]);
-        split_planes<NS>(a[2], a[3], q[1]);
-        split_planes<NS>(b[0], b[1], q[2]);
-        split_planes<NS>(b[2], b[3], q[3]);
-#pragma unroll
-        for (int s_ = 0; s_ < plane_count(NS); ++s_) {
-            u32x4 v = {q[0][s_], q[1][s_], q[2][s_], q[3][s_]};
-            *reinterpret_cast<u32x4*>(A + lrow * RS + s_ * 64 + lseg * 16) = v;
-        }
+        store_planes8<NS>(A + lrow * RS + lseg * 16, a, b);
         __builtin_amdgcn_s_waitcnt(0x0070);              // vmcnt(0) lgkmcnt(0)
     };
     auto dma_b = [&](int kt, char* B) {                    // this tile's 64 rows of the 128-row image tile
-        const char* src = Ws + ((size_t)(tn >> 1) * nk + kt) * (size_t)(GO_BN * RS) + (size_t)(tn & 1) * Cfg::B_BYTES;
-        for (int off = wave * 1024; off < Cfg::B_BYTES; off += 4 * 1024)
-            __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(src + off + lane * 16),
-                                             (__attribute__((address_space(3))) void*)(B + off), 16, 0, 0);
+        dma_tile<Cfg::B_BYTES, 4>(Ws + ((size_t)(tn >> 1) * nk + kt) * (size_t)(GO_BN * RS) + (size_t)(tn & 1) * Cfg::B_BYTES, B, wave, lane);
     };
-    static_assert(Cfg::B_BYTES % 1024 == 0, "half an image tile must be a whole number of 1 KiB DMA pieces");
     f32x16 acc[1][1];
-#pragma unroll
-    for (int r = 0; r < 16; ++r) acc[0][0][r] = 0.f;
+    zero_acc(acc);
     auto mma = [&](const char* A, const char* B) {
-        const char* pa = A + (wm * 32 + l31) * RS + half * 16;
-        const char* pb = B + (wn * 32 + l31) * RS + half * 16;
-#pragma unroll
-        for (int m = 0; m < 2; ++m) {
-            u32x4 a[plane_count(NS)], b[plane_count(NS)];
-#pragma unroll
-            for (int s_ = 0; s_ < plane_count(NS); ++s_) {
-                a[s_] = *reinterpret_cast<const u32x4*>(pa + s_ * 64 + m * 32);
-                b[s_] = *reinterpret_cast<const u32x4*>(pb + s_ * 64 + m * 32);
-            }
-#pragma unroll
-            for (int q = 0; q < Planes<NS>::NPROD; ++q) acc[0][0] = mfma_planes<NS>(a[Planes<NS>::A[q]], b[Planes<NS>::B[q]], acc[0][0]);
-        }
+        mma_k32<NS, 1, 1, RS>(A + (wm * 32 + l31) * RS + half * 16, B + (wn * 32 + l31) * RS + half * 16, acc);
         __builtin_amdgcn_s_waitcnt(0x0070);              // all fragment reads returned before a tile is overwritten
     };
     dma_b(0, smem + Cfg::A_BYTES);
@@ -946,37 +790,57 @@ __global__ __launch_bounds__(GO_THREADS, 3) void gemm_nt_bf16_small_kernel(GemmB
     gemm_epilogue<NS, 1, 1, false>(p, acc, m0, wm * 32, n0 + wn * 32, wm, wn * 32, 64, reinterpret_cast<float*>(smem), tid);
 }
 
+// ------------------------------------------------------------------------------------------ host side
+// One launch of a kernel with dynamic LDS: its LDS limit is raised once per device (the PerDevice flag is per instantiation, hence
+// per kernel), then the launch and its check
+template <auto Kernel, typename... Args>
+int launch_lds(int threads, int lds_bytes, int nblk, hipStream_t st, Args... args) {
+    static PerDevice attr_set{};
+    EV2H_ONCE_PER_DEVICE(attr_set,
+        EV2H_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(Kernel), hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes)););
+    Kernel<<<nblk, threads, lds_bytes, st>>>(args...);
+    EV2H_CHECK_LAUNCH();
+    return EV2H_OK;
+}
+
+// f(std::integral_constant<int, NS>) with the plane mode NS of a 16-bit precision
+template <typename F>
+int with_planes(int precision, F f) {
+    if (precision == EV2H_PREC_BF16X3) return f(std::integral_constant<int, 3>{});
+    if (precision == EV2H_PREC_F16X2) return f(std::integral_constant<int, 2>{});
+    if (precision == EV2H_PREC_BF16) return f(std::integral_constant<int, 1>{});
+    if (precision == EV2H_PREC_F16) return f(std::integral_constant<int, 4>{});
+    ev2h_set_error("ev2h_gemm: unknown precision %d", precision);
+    return EV2H_ERR_ARG;
+}
+
+template <int NS, bool GEN>
+int launch_gb(const GemmBP& p, hipStream_t st) {
+    return launch_lds<gemm_nt_bf16_kernel<NS, GEN>>(GB_THREADS, GBCfg<NS>::LDS_BYTES, p.nblk, st, p);
+}
+template <int NS>
+int launch_gw(const GemmBP& p, const char* Ws, hipStream_t st) {
+    return launch_lds<gemm_nt_bf16_wide_kernel<NS>>(GB_THREADS, GWCfg<NS>::LDS_BYTES, p.nblk, st, p, Ws);
+}
+template <int NS, bool TAP3, bool ZS = false>
+int launch_go_t(const GemmBP& p, const char* Ws, hipStream_t st) {
+    return launch_lds<gemm_nt_bf16_occ_kernel<NS, TAP3, false, ZS>>(GO_THREADS, GOCfg<NS, TAP3>::LDS_BYTES, p.nblk, st, p, Ws);
+}
+template <int NS>
+int launch_go_pipe(const GemmBP& p, const char* Ws, hipStream_t st) {
+    return launch_lds<gemm_nt_bf16_occ_kernel<NS, false, true>>(GO_THREADS, 2 * GOCfg<NS, false>::LDS_BYTES, p.nblk, st, p, Ws);
+}
 template <int NS>
 int launch_go_small(GemmBP p, const char* Ws, hipStream_t st) {
     p.tiles_n = ceil_div(p.N, 64);
     p.nblk = ceil_div(p.M, 64) * p.tiles_n;
-    static PerDevice attr_set{};
-    EV2H_ONCE_PER_DEVICE(attr_set,
-        EV2H_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_nt_bf16_small_kernel<NS>),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, GSCfg<NS>::LDS_BYTES)););
-    gemm_nt_bf16_small_kernel<NS><<<p.nblk, GO_THREADS, GSCfg<NS>::LDS_BYTES, st>>>(p, Ws);
-    EV2H_CHECK_LAUNCH();
-    return EV2H_OK;
-}
-
-template <int NS>
-constexpr int go_pipe_lds() { return 2 * GOCfg<NS, false>::LDS_BYTES; }
-
-template <int NS>
-int launch_go_pipe(const GemmBP& p, const char* Ws, hipStream_t st) {
-    static PerDevice attr_set{};
-    EV2H_ONCE_PER_DEVICE(attr_set,
-        EV2H_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_nt_bf16_occ_kernel<NS, false, true>),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, go_pipe_lds<NS>())););
-    gemm_nt_bf16_occ_kernel<NS, false, true><<<p.nblk, GO_THREADS, go_pipe_lds<NS>(), st>>>(p, Ws);
-    EV2H_CHECK_LAUNCH();
-    return EV2H_OK;
+    return launch_lds<gemm_nt_bf16_small_kernel<NS>>(GO_THREADS, GSCfg<NS>::LDS_BYTES, p.nblk, st, p, Ws);
 }
 
 template <int NS>
 int launch_go(const GemmBP& p, const char* Ws, hipStream_t st) {
-    // (the tap-reuse kernel for the shapes that tile; every other k = 3 shape -- N % 128 != 0 -- takes the plain K loop below, which the
-    //  odd-N end-to-end cases exercise: the EV2H_GEMM_NO_TAP3 switch of rounds 2-5 is retired)
+    // (the tap-reuse kernel for the shapes that tile; every other k = 3 shape -- channels no multiple of 32, sequences no multiple of
+    //  128 rows -- takes the plain K loop below: the K = 48 rows of test_gpu_ops.py::GEMM_CASES, the end-to-end cases with odd point counts)
     if (p.taps == 3 && p.Kc % GB_BK == 0 && p.rows_per_seq % GB_BM == 0 && p.M % p.rows_per_seq == 0)
         return launch_go_t<NS, true>(p, Ws, st);
     // (same sums in the same order in all three tilings: test_gpu_schedules.py::test_gemm_small_grids_bit_identical compares them through M)
@@ -985,11 +849,23 @@ int launch_go(const GemmBP& p, const char* Ws, hipStream_t st) {
     return launch_go_t<NS, false>(p, Ws, st);
 }
 
+// the fields both entry points fill the same way; range handling off (x_group_rows = y_group_rows = 1, no records)
+GemmBP base_params(const ev2h_gemm_desc* d) {
+    GemmBP p{};
+    p.X = d->X; p.ldx = d->ldx; p.W = d->W; p.ldw = d->ldw;
+    p.M = d->M; p.N = d->N; p.taps = d->taps; p.Kc = d->K; p.K = d->K * d->taps;
+    p.rows_per_seq = d->rows_per_seq;
+    p.bias = d->bias; p.relu = d->relu; p.post_scale = d->post_scale; p.post_shift = d->post_shift;
+    p.w_unscale = d->w_unscale > 0.f ? d->w_unscale : 1.f;
+    p.x_group_rows = p.y_group_rows = 1;
+    return p;
+}
+
 }  // namespace
 
 // geometry of the W plane images of the fast kernels (ev2h_tile_geometry): bytes per LDS row, K columns per tile
 int ev2h_gemm_tile_geometry(int ns, int out[2]) {
-    out[0] = ns == 1 ? GBCfg<1>::RS : ns == 2 ? GBCfg<2>::RS : ns == 3 ? GBCfg<3>::RS : GBCfg<4>::RS;
+    out[0] = ns == 1 ? GemmTile<1>::RS : ns == 2 ? GemmTile<2>::RS : ns == 3 ? GemmTile<3>::RS : GemmTile<4>::RS;
     out[1] = GB_BK;
     return EV2H_OK;
 }
@@ -1012,13 +888,7 @@ bool ev2h_gemm_bf16_zsum_supported(const ev2h_gemm_desc* d) {
 int ev2h_gemm_bf16_zsum(const ev2h_gemm_desc* d, const float* key_pm, float* zpart, int x_bf16, ev2h_stream_t stream, const float* x_scale) {
     EV2H_CHECK_ARG(d && key_pm && zpart && ev2h_gemm_bf16_zsum_supported(d));
     EV2H_CHECK_ARG(!x_bf16 || d->precision == EV2H_PREC_BF16 || (d->precision == EV2H_PREC_F16 && x_scale && d->x_group_rows > 0));
-    GemmBP p{};
-    p.X = d->X; p.ldx = d->ldx; p.W = d->W; p.ldw = d->ldw; p.Y = nullptr; p.ldy = 0;
-    p.M = d->M; p.N = d->N; p.taps = 3; p.Kc = d->K; p.K = d->K * 3;
-    p.rows_per_seq = d->rows_per_seq;
-    p.bias = d->bias; p.relu = d->relu; p.post_scale = d->post_scale; p.post_shift = d->post_shift;
-    p.w_unscale = d->w_unscale > 0.f ? d->w_unscale : 1.f;
-    p.x_group_rows = p.y_group_rows = 1;
+    GemmBP p = base_params(d);             // (taps == 3: ev2h_gemm_bf16_zsum_supported; no Y)
     if ((d->precision == EV2H_PREC_F16X2 || d->precision == EV2H_PREC_F16) && d->x_amax) {
         p.x_amax = d->x_amax; p.x_amax2 = d->x_amax2; p.x_group_rows = d->x_group_rows > 0 ? d->x_group_rows : 1;
     }
@@ -1027,25 +897,17 @@ int ev2h_gemm_bf16_zsum(const ev2h_gemm_desc* d, const float* key_pm, float* zpa
     if (x_bf16 && d->precision == EV2H_PREC_F16) { p.x_scale = x_scale; p.x_amax = p.x_amax2 = nullptr; p.x_group_rows = d->x_group_rows; }
     p.tiles_n = d->N / GO_BN;
     p.nblk = (d->M / GB_BM) * p.tiles_n;
-    if (d->precision == EV2H_PREC_F16X2) return launch_go_t<2, true, true>(p, (const char*)d->Ws, (hipStream_t)stream);
-    if (d->precision == EV2H_PREC_BF16) return launch_go_t<1, true, true>(p, (const char*)d->Ws, (hipStream_t)stream);
-    if (d->precision == EV2H_PREC_BF16X3) return launch_go_t<3, true, true>(p, (const char*)d->Ws, (hipStream_t)stream);
-    if (d->precision == EV2H_PREC_F16) return launch_go_t<4, true, true>(p, (const char*)d->Ws, (hipStream_t)stream);
-    return EV2H_ERR_ARG;
+    return with_planes(d->precision, [&](auto ns) { return launch_go_t<ns(), true, true>(p, (const char*)d->Ws, (hipStream_t)stream); });
 }
 
 // called by ev2h_gemm when d->precision != EV2H_PREC_F32 (arguments already validated there)
 int ev2h_gemm_bf16(const ev2h_gemm_desc* d, ev2h_stream_t stream) {
     EV2H_CHECK_ARG((d->K % 8) == 0);
     if (d->taps == 3) EV2H_CHECK_ARG((d->K % 16) == 0);       // a 16-float loader segment never straddles two taps
-    GemmBP p{};
-    p.X = d->X; p.ldx = d->ldx; p.W = d->W; p.ldw = d->ldw; p.Y = d->Y; p.ldy = d->ldy;
-    p.M = d->M; p.N = d->N; p.taps = d->taps; p.Kc = d->K; p.K = d->K * d->taps;
-    p.rows_per_seq = d->rows_per_seq;
-    p.bias = d->bias; p.bias_group_rows = d->bias_group_rows; p.ldbias = d->ldbias;
-    p.relu = d->relu; p.post_scale = d->post_scale; p.post_shift = d->post_shift;
+    GemmBP p = base_params(d);
+    p.Y = d->Y; p.ldy = d->ldy;
+    p.bias_group_rows = d->bias_group_rows; p.ldbias = d->ldbias;
     p.rowmax_rows = d->rowmax_rows;
-    p.w_unscale = d->w_unscale > 0.f ? d->w_unscale : 1.f;
     if (d->precision == EV2H_PREC_F16X2 || d->precision == EV2H_PREC_F16) {
         p.x_amax = d->x_amax; p.x_amax2 = d->x_amax2; p.x_group_rows = d->x_group_rows > 0 ? d->x_group_rows : 1;
         p.y_amax = d->y_amax; p.y_group_rows = d->y_group_rows > 0 ? d->y_group_rows : 1;
@@ -1053,40 +915,20 @@ int ev2h_gemm_bf16(const ev2h_gemm_desc* d, ev2h_stream_t stream) {
         if (!p.x_amax) { p.x_amax2 = nullptr; p.y_scale = nullptr; }
         if (p.y_scale) EV2H_CHECK_ARG(p.x_group_rows == p.y_group_rows && d->rowmax_rows == 0);
         if (d->taps == 3 && p.x_amax) EV2H_CHECK_ARG(p.x_group_rows % d->rows_per_seq == 0);   // a sequence never straddles two scales
-    } else {
-        p.x_group_rows = p.y_group_rows = 1;
     }
     // range groups that do not tile by 128 rows (N % 128 != 0, or one row per group: the per-window head layers) take the
     // generic kernel with the per-row epilogue; everything on the hot path is tile aligned
     const bool general = (p.x_amax && p.x_group_rows % GB_BM != 0) ||
                          (p.y_amax && d->rowmax_rows == 0 && p.y_group_rows % GB_BM != 0);
-    if (general) {
-        p.tiles_n = ceil_div(d->N, GB_BN);
-        p.nblk = ceil_div(d->M, GB_BM) * p.tiles_n;
-        return d->precision == EV2H_PREC_F16 ? launch_gb<4, true>(p, (hipStream_t)stream) : launch_gb<2, true>(p, (hipStream_t)stream);
-    }
-    if (d->Ws && d->ws_tile_rows == 128) {   // 128-row plane images: three small workgroups per CU
-        p.tiles_n = ceil_div(d->N, GO_BN);
-        p.nblk = ceil_div(d->M, GB_BM) * p.tiles_n;
-        if (d->precision == EV2H_PREC_BF16X3) return launch_go<3>(p, (const char*)d->Ws, (hipStream_t)stream);
-        if (d->precision == EV2H_PREC_F16X2) return launch_go<2>(p, (const char*)d->Ws, (hipStream_t)stream);
-        if (d->precision == EV2H_PREC_BF16) return launch_go<1>(p, (const char*)d->Ws, (hipStream_t)stream);
-        if (d->precision == EV2H_PREC_F16) return launch_go<4>(p, (const char*)d->Ws, (hipStream_t)stream);
-    }
-    if (d->Ws) {   // host-packed plane images of W: wide tile, W streamed by LDS-DMA
-        p.tiles_n = ceil_div(d->N, GW_BN);
-        p.nblk = ceil_div(d->M, GB_BM) * p.tiles_n;
-        if (d->precision == EV2H_PREC_BF16X3) return launch_gw<3>(p, (const char*)d->Ws, (hipStream_t)stream);
-        if (d->precision == EV2H_PREC_F16X2) return launch_gw<2>(p, (const char*)d->Ws, (hipStream_t)stream);
-        if (d->precision == EV2H_PREC_BF16) return launch_gw<1>(p, (const char*)d->Ws, (hipStream_t)stream);
-        if (d->precision == EV2H_PREC_F16) return launch_gw<4>(p, (const char*)d->Ws, (hipStream_t)stream);
-    }
-    p.tiles_n = ceil_div(d->N, GB_BN);
+    const char* Ws = general ? nullptr : (const char*)d->Ws;
+    hipStream_t st = (hipStream_t)stream;
+    const int tile_cols = !Ws ? GB_BN : d->ws_tile_rows == 128 ? GO_BN : GW_BN;
+    p.tiles_n = ceil_div(d->N, tile_cols);
     p.nblk = ceil_div(d->M, GB_BM) * p.tiles_n;
-    if (d->precision == EV2H_PREC_BF16X3) return launch_gb<3, false>(p, (hipStream_t)stream);
-    if (d->precision == EV2H_PREC_F16X2) return launch_gb<2, false>(p, (hipStream_t)stream);
-    if (d->precision == EV2H_PREC_BF16) return launch_gb<1, false>(p, (hipStream_t)stream);
-    if (d->precision == EV2H_PREC_F16) return launch_gb<4, false>(p, (hipStream_t)stream);
-    ev2h_set_error("ev2h_gemm: unknown precision %d", d->precision);
-    return EV2H_ERR_ARG;
+    if (general) return d->precision == EV2H_PREC_F16 ? launch_gb<4, true>(p, st) : launch_gb<2, true>(p, st);
+    return with_planes(d->precision, [&](auto ns) {
+        if (Ws && d->ws_tile_rows == 128) return launch_go<ns()>(p, Ws, st);   // 128-row plane images: three small workgroups per CU
+        if (Ws) return launch_gw<ns()>(p, Ws, st);                             // 256-row plane images: wide tile, one 8-wave workgroup
+        return launch_gb<ns(), false>(p, st);                                  // no image: W is split on the fly too
+    });
 }

@@ -82,6 +82,22 @@ __device__ __forceinline__ void split_planes(float x0, float x1, unsigned (&o)[p
     }
 }
 
+// 8 consecutive fp32 values of an operand row (already zero-filled and scaled) -> their plane_count(NS) 16-byte pieces in an LDS tile
+// row whose planes lie 64 bytes apart; dst = the piece of plane 0
+template <int NS>
+__device__ __forceinline__ void store_planes8(char* dst, f32x4 r0, f32x4 r1) {
+    unsigned q[4][plane_count(NS)];
+    split_planes<NS>(r0[0], r0[1], q[0]);
+    split_planes<NS>(r0[2], r0[3], q[1]);
+    split_planes<NS>(r1[0], r1[1], q[2]);
+    split_planes<NS>(r1[2], r1[3], q[3]);
+#pragma unroll
+    for (int s = 0; s < plane_count(NS); ++s) {
+        u32x4 v = {q[0][s], q[1][s], q[2][s], q[3][s]};
+        *reinterpret_cast<u32x4*>(dst + s * 64) = v;
+    }
+}
+
 // ReLU of two packed bf16 values in one v_pk_max_i16: a negative float's bf16 pattern is a negative int16 (-0 included)
 typedef short s16x2 __attribute__((ext_vector_type(2)));
 __device__ __forceinline__ unsigned relu_pk_bf16(unsigned v) {

@@ -180,8 +180,8 @@ typedef struct ev2h_gemm_desc {
     int rows_per_seq;            /* rows per window when taps == 3                                      */
     int rowmax_rows;             /* 0, or 128: write max over each 128-row group (group-all set abstraction) */
     int precision;               /* EV2H_PREC_*; all but F32 need K % 8 == 0 (operands are split on the fly), K % 16 == 0 with taps == 3 */
-    const void* Ws;              /* optional, BF16 / BF16X3: bf16 plane images of W in (ws_tile_rows)-row x 32-k LDS
-                                    tiles (ev2h_pack_gemm_image); NULL = split W on the fly  */
+    const void* Ws;              /* optional, every 16-bit precision (BF16, BF16X3, F16X2, F16): that mode's plane images of W in
+                                    (ws_tile_rows)-row x 32-k LDS tiles (ev2h_pack_gemm_image); NULL = split W on the fly  */
     int ws_tile_rows;            /* 128 (three 4-wave workgroups per CU) or 256 (one 8-wave workgroup)           */
     float w_unscale;             /* 16-bit precisions: W is used as W / w_unscale (Ws holds those planes) and the product is
                                     multiplied by w_unscale before the bias; a power of two chosen by the host so that the

@@ -178,6 +178,14 @@ GEMM_CASES = [
     (256, 512, 256, True, False, 1, 128, 0),
     (384, 256, 512, True, False, 1, 0, 128),
     (4096, 256, 576, True, False, 1, 0, 0),
+    # k = 3 at a ragged N.  K = 32: 128-row images take the tap-reuse kernel (gload3) with a ragged last tile column; 256-row images and
+    # the image-free row go through the operand-row address step the kernels share (gemm_bf16.hip: x_operand) in the wide / generic kernel
+    (256, 160, 32, True, False, 3, 0, 0),
+    (8448, 160, 32, True, False, 3, 0, 0),        # 66 x 2 = 132 workgroups, 256-row sequences
+    (256, 64, 32, False, False, 3, 0, 0),         # N < 96: no image, the generic kernel
+    # K % 32 != 0: 128-row images leave the tap-reuse kernel for the plain K loop over x_operand -- pipelined (4 workgroups), single-buffer (132)
+    (256, 160, 48, True, False, 3, 0, 0),
+    (8448, 160, 48, True, False, 3, 0, 0),
 ]
 
 
