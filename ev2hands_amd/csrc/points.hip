@@ -261,6 +261,7 @@ __global__ __launch_bounds__(256) void ball_query_kernel(const float4* __restric
 
 // ---------------------------------------------------------------------------------------- 3-NN interpolation
 constexpr int NN_PTS_PER_WG = 256;
+constexpr int NN_MAX_N2 = 4096;           // coarse points staged in LDS: the entry check and the raised dynamic-LDS limit
 
 __global__ __launch_bounds__(256) void three_nn_interp_kernel(const float4* __restrict__ pts1, const float4* __restrict__ pts2,
                                                               int N1, int N2, const float* __restrict__ feat2, int ldf2, int D,
@@ -472,11 +473,17 @@ extern "C" int ev2h_three_nn_interp(const float* pts1_4, const float* pts2_4, in
                                     int ldf2, int D, float* out, int ldo, int32_t* nn_idx, float* nn_w, uint32_t* out_amax,
                                     ev2h_stream_t stream) {
     EV2H_CHECK_ARG(pts1_4 && pts2_4);
-    EV2H_CHECK_ARG(B > 0 && N1 > 0 && N2 >= 3 && N2 <= 4096);
+    EV2H_CHECK_ARG(B > 0 && N1 > 0 && N2 >= 3 && N2 <= NN_MAX_N2);
     if (out) EV2H_CHECK_ARG(feat2 && D > 0 && (D % 4) == 0 && (ldf2 % 4) == 0 && (ldo % 4) == 0);
     const int ppw = ((long)ceil_div(N1, NN_PTS_PER_WG) * B < 128) ? 64 : NN_PTS_PER_WG;
     dim3 grid(ceil_div(N1, ppw), B);
     const size_t lds = (size_t)N2 * sizeof(float4) + NN_PTS_PER_WG * 3 * (sizeof(int) + sizeof(float));
+    if (lds > 64 * 1024) {         // N2 > 3712 (the entry check admits NN_MAX_N2: 70 KiB): raise the dynamic-LDS limit once, as the sampling does
+        static PerDevice attr_set{};
+        EV2H_ONCE_PER_DEVICE(attr_set,
+            EV2H_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(three_nn_interp_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                               NN_MAX_N2 * (int)sizeof(float4) + NN_PTS_PER_WG * 3 * (int)(sizeof(int) + sizeof(float)))););
+    }
     three_nn_interp_kernel<<<grid, 256, lds, (hipStream_t)stream>>>((const float4*)pts1_4, (const float4*)pts2_4, N1, N2, feat2,
                                                                     ldf2, D, out, ldo, nn_idx, nn_w, out_amax, ppw);
     EV2H_CHECK_LAUNCH();
