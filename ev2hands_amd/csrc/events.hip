@@ -8,6 +8,13 @@
 // so a float atomicAdd scatter would not be bit-identical.  One workgroup per window instead sorts 32-bit keys (pixel << 15 | event index) with a bitonic network
 // in LDS (<= 32768 events per window); equal-pixel events end up adjacent and in stream order, every run is summed
 // sequentially in fp32 by the thread that owns its first element, and the runs come out already in np.nonzero order.
+//
+// The contract at its edges (include/ev2hands_hip.h; tests/ref_events.py restates it): a sensor has at most 131071 pixels (the two
+// largest keys are reserved, see EVW_MAX_PIXELS); x and y are truncated towards zero; an event outside the sensor, or with a NaN or
+// infinite coordinate, is dropped; the time subtracted (raw_time = 0) is that of the window's first row, dropped or not; polarity
+// == 1 is positive, anything else negative; the count is the full number of pixels hit, the table holds the first `cap` of them and
+// rows beyond are left alone; the time sort takes min(M, cap) rows; the sampler maps an index outside [0, min(M, cap)) to row 0 and
+// the seeded sampler refuses a window with M outside [1, cap].
 #include "common.hpp"
 #include "ev2hands_hip.h"
 #include "random.hpp"
@@ -16,6 +23,9 @@ namespace {
 
 constexpr int EVW_THREADS = 1024;
 constexpr int EVW_MAX_EVENTS = 32768;
+// A key is (pixel << 15) | event index, and 0xfffffffe / 0xffffffff are taken (dropped event / padding): pixel 131071 with event
+// 32766 or 32767 would pack to exactly those two.  So the last pixel a sensor may have is 131070.
+constexpr long long EVW_MAX_PIXELS = (1 << 17) - 1;
 
 // ascending bitonic sort of n (a power of two) 32-bit keys in LDS by the whole workgroup
 __device__ __forceinline__ void bitonic_sort_u32(unsigned* keys, int n, int tid) {
@@ -52,9 +62,12 @@ __device__ __forceinline__ bool event_window_build_body(const double* __restrict
     for (int i = tid; i < n; i += EVW_THREADS) {
         unsigned k = 0xffffffffu;
         if (i < E) {
-            const int x = (int)ev[(size_t)i * ev_stride + 0], y = (int)ev[(size_t)i * ev_stride + 1];     // .astype(np.int32): truncation
-            const bool ok = x >= 0 && x < width && y >= 0 && y < height;
-            k = ok ? ((unsigned)(y * width + x) << 15) | (unsigned)i : 0xfffffffeu;           // out-of-sensor events are dropped
+            // .astype(np.int32) truncates towards zero, so the pixel is inside the sensor exactly when -1 < x < width and -1 < y < height
+            // (-0.5 is column 0, width - 0.001 is the last one).  Tested on the doubles: a NaN fails every comparison, +-inf and 1e10
+            // fail one, and the conversion below only ever sees a value an int holds.
+            const double dx = ev[(size_t)i * ev_stride + 0], dy = ev[(size_t)i * ev_stride + 1];
+            const bool ok = dx > -1.0 && dx < (double)width && dy > -1.0 && dy < (double)height;
+            k = ok ? ((unsigned)((int)dy * width + (int)dx) << 15) | (unsigned)i : 0xfffffffeu;     // out-of-sensor and non-finite events are dropped
         }
         keys[i] = k;
     }
@@ -327,8 +340,9 @@ __global__ __launch_bounds__(256) void event_window_sample_seeded_kernel(const f
 
 extern "C" int ev2h_event_window_build(const double* events, int ev_stride, const int32_t* offsets, int B, int width, int height, int cap,
                                        int raw_time, int32_t* uniq_count, float* uniq, ev2h_stream_t stream) {
+    EV2H_CHECK_ARG(width > 0 && height > 0 && (long long)width * height <= EVW_MAX_PIXELS);
     EV2H_CHECK_ARG(events && offsets && uniq_count && uniq && ev_stride >= 4);
-    EV2H_CHECK_ARG(B > 0 && width > 0 && height > 0 && width * height <= (1 << 17) && cap > 0);
+    EV2H_CHECK_ARG(B > 0 && cap > 0);
     static PerDevice attr_set{};
     EV2H_ONCE_PER_DEVICE(attr_set,
         EV2H_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(event_window_build_kernel),
@@ -341,8 +355,9 @@ extern "C" int ev2h_event_window_build(const double* events, int ev_stride, cons
 extern "C" int ev2h_event_window_build_ranges(const double* events, int ev_stride, int n_rows, const int32_t* starts, const int32_t* ends, int B,
                                               int width, int height, int cap, int frame_col, int32_t* uniq_count, float* uniq,
                                               int32_t* frame_index, int32_t* first_frame, ev2h_stream_t stream) {
+    EV2H_CHECK_ARG(width > 0 && height > 0 && (long long)width * height <= EVW_MAX_PIXELS);
     EV2H_CHECK_ARG(events && starts && ends && uniq_count && uniq && frame_index && first_frame && ev_stride >= 4 && n_rows > 0);
-    EV2H_CHECK_ARG(B > 0 && width > 0 && height > 0 && width * height <= (1 << 17) && cap > 0 && frame_col < ev_stride);
+    EV2H_CHECK_ARG(B > 0 && cap > 0 && frame_col < ev_stride);
     static PerDevice attr_set{};
     EV2H_ONCE_PER_DEVICE(attr_set,
         EV2H_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(event_window_build_ranges_kernel),

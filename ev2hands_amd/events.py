@@ -25,7 +25,10 @@ class EventWindowBuilder:
         self.raw_time = 0            # evaluation builders subtract the window's first timestamp before accumulating
 
     def accumulate(self, windows):
-        """windows: list of [E_i, >=4] float64 arrays (x, y, t, polarity, ...).  Returns (table [B,cap,8] f32, counts [B] i32), on device."""
+        """windows: list of [E_i, >=4] float64 arrays (x, y, t, polarity, ...).  Returns (table [B,cap,8] f32, counts [B] i32), on device.
+        The sensor has at most 131071 pixels.  x and y are truncated towards zero; an event outside the sensor, or with a NaN or infinite
+        coordinate, is dropped; the time subtracted is that of the window's first row, dropped or not.  counts[b] is the full number of
+        pixels hit (0: none, -1: more than 32768 events); the table holds the first `cap` of them."""
         B = len(windows)
         offs = np.zeros(B + 1, dtype=np.int32)
         offs[1:] = np.cumsum([w.shape[0] for w in windows])
@@ -65,12 +68,14 @@ class EventWindowBuilder:
     def sample(self, table, counts, sample_idx=None, labels=None):
         """-> float32 [B, 5, N] (and int64 [B, N] labels when the per-pixel `labels` [B, cap] int32 are given).  sample_idx [B, N]
         (any integer type); None draws np.random.choice(M_b, N) per window in batch order from numpy's global RNG
-        (evaluation_stream.py:209)."""
+        (evaluation_stream.py:209) and raises if a window cannot be drawn from: count 0 (empty, or every event outside the sensor),
+        -1 (more than 32768 events) or above `cap` (the table was truncated).  Explicit indices are the caller's: the kernel reads
+        row 0 for every index outside [0, min(M, cap))."""
         B = table.shape[0]
         if sample_idx is None:
             ms = counts.cpu().numpy()
-            if (ms <= 0).any():
-                raise RuntimeError("an event window is empty or exceeds 32768 events")
+            if (ms <= 0).any() or (ms > self.cap).any():          # the table holds `cap` rows: an index drawn from [0, M) beyond them would read row 0
+                raise RuntimeError("an event window is empty, exceeds 32768 events or has more unique pixels than `cap`")
             sample_idx = np.stack([np.random.choice(int(m), self.n) for m in ms])
         idx = torch.as_tensor(np.asarray(sample_idx), dtype=torch.int32).to(self.device).contiguous()
         n = idx.shape[1]

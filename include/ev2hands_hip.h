@@ -384,9 +384,23 @@ int ev2h_mano_rotations(const ev2h_mano_consts* c, const float* params, int ldp,
 /* Per-pixel accumulation + np.nonzero-order compaction of B ragged windows.  events: device float64 rows of ev_stride (>= 4)
  * columns (x, y, t, polarity, ...) in stream order, exactly the arrays the reference builds; offsets: device [B+1] row offsets
  * (<= 32768 events per window).  uniq [B][cap][8] float32 records (x, y, t_avg, pos_cnt, neg_cnt, 0, 0, 0) of the pixels hit, in
- * row-major pixel order; uniq_count [B] (-1 if a window is too large).  Bit-identical to np.add.at / np.nonzero.
+ * row-major pixel order; uniq_count [B] (-1 if a window is too large, 0 for an empty one).  Bit-identical to np.add.at / np.nonzero.
  * raw_time = 0: evaluation builders (t minus the window's first timestamp, evaluation_stream.py:187);
- * raw_time = 1: Ev2Hands-S builder (timestamps as they are, mean times 1e-6, erpc.py:178-191). */
+ * raw_time = 1: Ev2Hands-S builder (timestamps as they are, mean times 1e-6, erpc.py:178-191).
+ * The contract at its edges (tests/ref_events.py restates it, tests/test_gpu_events_edges.py holds the kernels to it):
+ *   sensor     width * height <= 131071 = (1 << 17) - 1, EV2H_ERR_ARG above: a sort key is (pixel << 15) | event index and its two
+ *              largest values are reserved, which pixel 131071 with events 32766 / 32767 would collide with (512 x 256 is refused).
+ *   x, y       truncated towards zero (.astype(np.int32), :193): -0.5 is column 0, width - 0.001 the last column.  An event whose
+ *              truncated pixel lies outside [0, width) x [0, height), or whose x or y is not finite (NaN, +-inf), is DROPPED: it
+ *              adds to no pixel.  A window all of whose events are dropped has uniq_count 0.
+ *   t          raw_time = 0 subtracts the time of the window's FIRST ROW, whether or not that row is dropped.
+ *   polarity   == 1 counts as positive, every other value (0, -1, 2, 0.5, NaN) as negative.
+ *   columns    beyond the fourth are never read (ev2h_event_window_timesort reads label_col).
+ *   cap < M    uniq_count is the full number M of pixels hit; the table holds the first `cap` of them in row-major order, rows at
+ *              and beyond `cap` are not written.  ev2h_event_window_timesort sorts those first min(M, cap) rows.
+ *              ev2h_event_window_sample maps every index outside [0, min(M, cap)) to row 0 -- it cannot report anything, so the
+ *              caller must not draw indices from [0, M) when M > cap (EventWindowBuilder.sample raises instead).
+ *              ev2h_event_window_sample_seeded refuses such a window: zeros, and its id in *status. */
 int ev2h_event_window_build(const double* events, int ev_stride, const int32_t* offsets, int B, int width, int height, int cap,
                             int raw_time, int32_t* uniq_count, float* uniq, ev2h_stream_t stream);
 /* Ev2Hands-S only (erpc.py:207-211): unique pixels re-ordered by mean time (np.argsort; exactly equal times keep pixel order --
@@ -470,7 +484,9 @@ int ev2h_event_stream_walk(const int32_t* end, const int32_t* next, int n_rows, 
 /* ev2h_event_window_build (raw_time = 0) for the B windows rows starts[b] .. ends[b]-1 of a recording (device arrays, e.g. slices of
  * ev2h_event_stream_walk's): the kernel scales and shifts the timestamps itself, t_ms(i) - t_ms(starts[b]) with both products
  * rounded first (:102,187), and writes the table and count that ev2h_event_window_build writes for the host-cut, host-scaled copy
- * of those rows, bit for bit (-1 above 32768 rows; 0 for a range that is empty or outside the recording).  frame_col >= 4: column
+ * of those rows, bit for bit (-1 above 32768 rows; 0 for a range that is empty or outside the recording).  The same sensor limit
+ * (width * height <= 131071), the same dropping of out-of-sensor and non-finite rows, the same `cap`; the time subtracted is that of
+ * row starts[b], dropped or not.  frame_col >= 4: column
  * of the frame index; frame_index [B] = its most frequent value in the window, the smallest on ties (:221-222), first_frame [B] =
  * its smallest value (the row of `joints` that :183-184 picks).  Both are -1 when frame_col < 0 (:95-98) or no table was built. */
 int ev2h_event_window_build_ranges(const double* events, int ev_stride, int n_rows, const int32_t* starts, const int32_t* ends, int B,
