@@ -4,6 +4,8 @@
 // MPJPE, best-of-G ground-truth candidate by right-root-relative AUC, first one on ties).
 // One wavefront per frame: lanes 0..41 own one joint each (hand = lane / 21); thresholds are tested with wave ballots.
 // Distances are taken in float64 like the reference (float32 predictions * 1000 against float64 ground truth * 1000).
+#include <cfloat>
+
 #include "common.hpp"
 #include "ev2hands_hip.h"
 
@@ -28,11 +30,13 @@ __device__ __forceinline__ double wave_sum_f64(double v) {
     }
     return v;
 }
+// minimum that propagates NaN like torch.min (fmin would return the other operand): every lane ends with NaN if any lane held one
 __device__ __forceinline__ double wave_min_f64(double v) {
 #pragma unroll
     for (int o = 32; o >= 1; o >>= 1) {
         const int lo = __shfl_xor(__double2loint(v), o, 64), hi = __shfl_xor(__double2hiint(v), o, 64);
-        v = fmin(v, __hiloint2double(hi, lo));
+        const double w = __hiloint2double(hi, lo);
+        v = (w < v || w != w) ? w : v;
     }
     return v;
 }
@@ -144,7 +148,7 @@ extern "C" int ev2h_joint_metrics(const float* j3d_left, const float* j3d_right,
                                   double dist_max_mm, float* pck, double* auc, double* mpjpe, double* root_distance, int32_t* best,
                                   ev2h_stream_t stream) {
     EV2H_CHECK_ARG(j3d_left && j3d_right && j3d_gts && pck && auc && mpjpe && root_distance && best);
-    EV2H_CHECK_ARG(B > 0 && G > 0 && num_steps > 0 && dist_max_mm > 0);
+    EV2H_CHECK_ARG(B > 0 && G > 0 && num_steps > 0 && dist_max_mm > 0 && dist_max_mm <= DBL_MAX);     // (NaN fails > 0)
     MetP p{j3d_left, j3d_right, j3d_gts, B, G, num_steps, dist_max_mm, pck, auc, mpjpe, root_distance, best};
     joint_metrics_kernel<<<B, 64, 0, (hipStream_t)stream>>>(p);
     EV2H_CHECK_LAUNCH();
@@ -155,7 +159,7 @@ extern "C" int ev2h_joint_metrics_frames(const float* j3d_left, const float* j3d
                                          int B, int num_steps, double dist_max_mm, float* pck, double* auc, double* mpjpe,
                                          double* root_distance, int32_t* has_gt, ev2h_stream_t stream) {
     EV2H_CHECK_ARG(j3d_left && j3d_right && joints && first_frame && pck && auc && mpjpe && root_distance && has_gt);
-    EV2H_CHECK_ARG(B > 0 && F > 0 && num_steps > 0 && dist_max_mm > 0);
+    EV2H_CHECK_ARG(B > 0 && F > 0 && num_steps > 0 && dist_max_mm > 0 && dist_max_mm <= DBL_MAX);
     MetP p{j3d_left, j3d_right, joints, B, 1, num_steps, dist_max_mm, pck, auc, mpjpe, root_distance, nullptr};
     joint_metrics_frames_kernel<<<B, 64, 0, (hipStream_t)stream>>>(p, first_frame, F, has_gt);
     EV2H_CHECK_LAUNCH();

@@ -497,15 +497,26 @@ int ev2h_event_window_build_ranges(const double* events, int ev_stride, int n_ro
 /* j3d_left / j3d_right [B][21][3] float32 metres (the forward's outputs); j3d_gts [B][G][2][21][3] float64 metres (G ground-truth
  * candidates per frame).  For the candidate with the best rounded right-root-relative AUC (first on ties): pck [B][3][num_steps+1]
  * (absolute, relative, right-root-relative), auc [B][3] (trapezoid / n, NOT yet rounded), mpjpe [B] (mm), root_distance [B] (mm),
- * best [B]. */
+ * best [B].
+ * Rules at the edges (tests/ref_metrics.py restates them, tests/golden/metrics_edges_0.npz pins them to the reference):
+ *   - a joint counts at step s when its distance is STRICTLY below (dist_max_mm / num_steps) * s, the product formed in that order;
+ *     a curve value is float32(k) / 42.  prediction * 1000 and prediction - root are float32, everything behind them float64;
+ *   - B, G, num_steps >= 1; dist_max_mm must be positive and finite (NaN, +-Inf, 0 and negatives are EV2H_ERR_ARG: an infinite
+ *     dist_max_mm would make the threshold of step 0 NaN);
+ *   - non-finite joints: a NaN or Inf distance is below no threshold, so that joint counts at no step (a NaN in a predicted root
+ *     takes every joint measured from that root out of the relative curves); mpjpe is NaN (Inf for an Inf prediction) like the
+ *     mean it is; root_distance is the minimum over the chosen candidate's 21 joint pairs and propagates NaN like torch.min: NaN
+ *     if any joint of the chosen candidate is NaN.  A candidate that is not chosen has no influence.  The rounded AUCs that
+ *     choose the candidate are never NaN. */
 int ev2h_joint_metrics(const float* j3d_left, const float* j3d_right, const double* j3d_gts, int B, int G, int num_steps,
                        double dist_max_mm, float* pck, double* auc, double* mpjpe, double* root_distance, int32_t* best,
                        ev2h_stream_t stream);
 /* ev2h_joint_metrics with the ground truth looked up on the device: joints [F][2][21][3] float64 metres is a recording's table,
  * and the ONE candidate of window b is its row first_frame[b] (device int32 [B], ev2h_event_window_build_ranges') -- np.unique
  * sorts the window's frame values and [:1] keeps the smallest (evaluation_stream.py:148-157,183-184), so G = 1.  has_gt [B] = 0
- * where first_frame[b] lies outside [0, F): that window's outputs are zeros and nothing is read.  pck, auc, mpjpe and
- * root_distance as above. */
+ * where first_frame[b] lies outside [0, F) -- any int32, INT32_MIN and INT32_MAX included; rows may repeat and come in any order --:
+ * that window's outputs are zeros and nothing of `joints` is read.  pck, auc, mpjpe and root_distance as above, with the same
+ * rules: dist_max_mm must be positive and finite, root_distance propagates NaN. */
 int ev2h_joint_metrics_frames(const float* j3d_left, const float* j3d_right, const double* joints, int F, const int32_t* first_frame,
                               int B, int num_steps, double dist_max_mm, float* pck, double* auc, double* mpjpe,
                               double* root_distance, int32_t* has_gt, ev2h_stream_t stream);
