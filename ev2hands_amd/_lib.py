@@ -90,7 +90,8 @@ W_EQUALIZED, W_UNEQUALIZED_OK = 1, 2
 # The demo-frame exports (ev2h_event_window_pixels, ev2h_demo_point_panels, ev2h_render_*) are purely additive -- no struct or existing
 # signature changed -- so the version stays 8.  The same holds for the recording exports (ev2h_event_stream_*, ev2h_event_window_build_ranges)
 # and for the seeded-draw / recording-evaluation exports (ev2h_event_window_sample_seeded, ev2h_fps_init_seeded, ev2h_joint_metrics_frames,
-# ev2h_eval_accumulate), and for ev2h_events_undistort.
+# ev2h_eval_accumulate), and for ev2h_events_undistort, and for the synthetic-set evaluation exports (ev2h_event_window_build_s_ranges,
+# ev2h_joint_metrics_f32_frames, ev2h_segmentation_score, ev2h_eval_s_accumulate).
 ABI_VERSION = 8     # 8: EV2H_PREC_F16 (one fp16 plane with f16x2's range machinery); 3: F16X2 range records; 4: ev2h_fp_mlp, ev2h_weights.fp1m; 5: window strides of the outputs; 6: ev2h_pack_weights, ev2h_weights.flags; 7: ev2h_sa_desc.xyz_out
 
 PREC = {"f32": 0, "bf16": 1, "f16x2": 2, "bf16x3": 3, "f16": 4}
@@ -121,6 +122,7 @@ EXPORTS = [
     "ev2h_event_stream_links", "ev2h_event_stream_ends", "ev2h_event_stream_walk", "ev2h_event_window_build_ranges",
     "ev2h_event_window_sample_seeded", "ev2h_fps_init_seeded", "ev2h_joint_metrics_frames", "ev2h_eval_accumulate",
     "ev2h_events_undistort",
+    "ev2h_event_window_build_s_ranges", "ev2h_joint_metrics_f32_frames", "ev2h_segmentation_score", "ev2h_eval_s_accumulate",
 ]
 
 _lib = None
@@ -207,6 +209,10 @@ def lib() -> C.CDLL:
     L.ev2h_fps_init_seeded.argtypes = [C.c_uint64, vp, ci, ci, ci, vp, vp]
     L.ev2h_joint_metrics_frames.argtypes = [vp, vp, vp, ci, vp, ci, ci, C.c_double, vp, vp, vp, vp, vp, vp]
     L.ev2h_eval_accumulate.argtypes = [vp] * 8 + [ci] * 4 + [vp] * 7 + [vp]
+    L.ev2h_event_window_build_s_ranges.argtypes = [vp, ci, ci, vp, ci, ci, ci, ci, ci, ci, ci, vp, vp, vp, vp, vp, vp]
+    L.ev2h_joint_metrics_f32_frames.argtypes = [vp, vp, C.c_size_t, vp, ci, vp, ci, ci, C.c_double, vp, vp, vp, vp, vp]
+    L.ev2h_segmentation_score.argtypes = [vp, C.c_size_t, vp, ci, ci, vp, vp, vp, vp, vp]
+    L.ev2h_eval_s_accumulate.argtypes = [vp] * 10 + [ci] * 4 + [vp] * 8 + [vp]
     L.ev2h_event_window_pixels.argtypes = [vp, vp, ci, vp, ci, ci, vp, vp, vp, vp]
     L.ev2h_demo_point_panels.argtypes = [vp, vp, vp, vp, C.c_size_t, ci, ci, ci, ci, vp, ci, ci, ci, vp]
     L.ev2h_render_scratch_bytes.restype = C.c_size_t

@@ -241,6 +241,24 @@ __global__ __launch_bounds__(EVW_THREADS) void event_window_timesort_kernel(cons
     }
 }
 
+// Ev2Hands-S windows cut on the device (erpc.py:170-176,200): window b = rows starts[b] .. min(starts[b] + n_events, n_rows) - 1 of a
+// resident table, accumulated as event_window_build_kernel does with raw_time = 1.  annotation[b] = the annotation column of the
+// window's LAST row.  A start outside [0, n_rows) is an empty window (count 0, annotation -1).
+__global__ __launch_bounds__(EVW_THREADS) void event_window_build_s_ranges_kernel(const double* __restrict__ events, int ev_stride, int n_rows,
+                                                                                  const int32_t* __restrict__ starts, int n_events, int width,
+                                                                                  int height, int cap, int anno_col,
+                                                                                  int32_t* __restrict__ uniq_count, float* __restrict__ uniq,
+                                                                                  int32_t* __restrict__ annotation) {
+    extern __shared__ __attribute__((aligned(16))) char smem_raw[];
+    __shared__ int s_part[EVW_THREADS];
+    const int b = blockIdx.x;
+    const int s = starts[b];
+    const int E = (s >= 0 && s < n_rows) ? min(n_events, n_rows - s) : 0;
+    const double* ev = events + (size_t)(E ? s : 0) * ev_stride;
+    event_window_build_body<false>(ev, E, b, width, height, cap, 1, ev_stride, uniq_count, uniq, reinterpret_cast<unsigned*>(smem_raw), s_part);
+    if (threadIdx.x == 0) annotation[b] = E ? (int32_t)ev[(size_t)(E - 1) * ev_stride + anno_col] : -1;
+}
+
 __global__ __launch_bounds__(256) void event_window_sample_kernel(const float* __restrict__ uniq, const int32_t* __restrict__ uniq_count, int cap,
                                                                   const int32_t* __restrict__ sample_idx, int N, int width, int height,
                                                                   float* __restrict__ out_cm, const int32_t* __restrict__ uniq_labels,
@@ -381,6 +399,25 @@ extern "C" int ev2h_event_window_timesort(const float* uniq_in, const int32_t* u
                                                                                        offsets, uniq_out, labels_out);
     EV2H_CHECK_LAUNCH();
     return EV2H_OK;
+}
+
+extern "C" int ev2h_event_window_build_s_ranges(const double* events, int ev_stride, int n_rows, const int32_t* starts, int B, int n_events,
+                                                int width, int height, int cap, int anno_col, int label_col, int32_t* uniq_count,
+                                                float* uniq_scratch, float* uniq_sorted, int32_t* labels, int32_t* annotation,
+                                                ev2h_stream_t stream) {
+    EV2H_CHECK_ARG(width > 0 && height > 0 && (long long)width * height <= EVW_MAX_PIXELS);
+    EV2H_CHECK_ARG(events && starts && uniq_count && uniq_scratch && uniq_sorted && labels && annotation && uniq_scratch != uniq_sorted);
+    EV2H_CHECK_ARG(B > 0 && n_rows > 0 && n_events > 0 && n_events <= EVW_MAX_EVENTS && cap > 0 && cap <= EVS_MAX);
+    EV2H_CHECK_ARG(ev_stride >= 4 && anno_col >= 0 && anno_col < ev_stride && label_col >= 0 && label_col < ev_stride);
+    static PerDevice attr_set{};
+    EV2H_ONCE_PER_DEVICE(attr_set,
+        EV2H_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(event_window_build_s_ranges_kernel),
+                                           hipFuncAttributeMaxDynamicSharedMemorySize, EVW_MAX_EVENTS * 4)););
+    event_window_build_s_ranges_kernel<<<B, EVW_THREADS, EVW_MAX_EVENTS * 4, (hipStream_t)stream>>>(events, ev_stride, n_rows, starts, n_events, width, height,
+                                                                                                    cap, anno_col, uniq_count, uniq_scratch, annotation);
+    EV2H_CHECK_LAUNCH();
+    // the time sort reads offsets[b] only, i.e. the window's first row: `starts` as they are.  An empty window has count 0 and is skipped there.
+    return ev2h_event_window_timesort(uniq_scratch, uniq_count, cap, events, ev_stride, label_col, starts, B, uniq_sorted, labels, stream);
 }
 
 extern "C" int ev2h_event_window_sample(const float* uniq, const int32_t* uniq_count, int cap, const int32_t* sample_idx, int B, int N,

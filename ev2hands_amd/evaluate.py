@@ -34,6 +34,7 @@ from . import _lib, synth
 from .collision import device_faces
 from .dist import packed_width
 from .events import EventWindowBuilder
+from .metrics import _dev_tensor, joint_metrics_f32_frames, segmentation_score
 from .model import TEHNet
 from .stream import StreamCut
 
@@ -246,5 +247,293 @@ class RecordingEvaluator:
         """stream: ev2hands_amd.stream.EventStream with a frame column; cut: its windows (default stream.cut()).  -> the metrics dict."""
         self.begin(stream, cut, window_ids)
         for sl in self._run["cut"].batches(self.batch):
+            self.step(sl)
+        return self.finish()
+
+
+# ------------------------------------------------------------------------------------------------ the synthetic test set
+SEG_CLASS_WEIGHTS = (1.0, 30.0, 30.0, 10.0)            # losses.py:203 (class 0 is the ignore_index: its weight is never used)
+
+
+def round_auc_s(pck: np.ndarray) -> float:
+    """get_auc of evaluate.py:237-241: sklearn.metrics.auc(range(n), pck) / n -- the trapezoid rule over unit steps -- then the
+    built-in round(.., 2) on the numpy float64 the reference has at that point (numpy's rule: rint(x * 100) / 100)"""
+    pck = np.asarray(pck, dtype=np.float64)
+    return round(np.sum((pck[1:] + pck[:-1]) * 0.5) / pck.shape[0], 2)
+
+
+def annotation_table(annotations, ncomps: int = synth.MANO_CMPS) -> np.ndarray:
+    """The reference's annotation dict (the `_anno.pickle` of an Ev2Hands-S sequence: annotation index -> {'left' | 'right':
+    {'global_orient' [1, 3], 'hand_pose' [1, >= ncomps], 'shape' [1, 10], 'trans' [1, 3]}}; a list works as well) as one float32
+    table [A, 2, 3 + ncomps + 10 + 3], hand 0 = left, columns (global_orient, hand_pose, shape, trans): what
+    Ev2HandSDataset.__getitem__ hands to the hand layers (dataset/erpc.py:266-292).  A missing hand takes the other hand's
+    parameters (:284-292; `valid` is ignored, as evaluate_net ignores it); hand_pose is cut to `ncomps` components, as manopth does
+    with a longer vector.  The indices must be 0 .. A-1: the scorer looks a window's row up by its annotation index."""
+    items = dict(enumerate(annotations)) if isinstance(annotations, (list, tuple)) else dict(annotations)
+    keys = sorted(int(k) for k in items)
+    if not keys or keys != list(range(len(keys))) or any(int(k) != k for k in items):
+        raise ValueError("the annotation indices must be exactly 0 .. A-1")
+    items = {int(k): v for k, v in items.items()}
+    P = 3 + ncomps + 10 + 3
+    out = np.zeros((len(keys), 2, P), dtype=np.float32)
+    for a in keys:
+        info = items[a]
+        hands = {s: info[s] for s in ("left", "right") if s in info}
+        if not hands:
+            raise ValueError(f"annotation {a} has neither hand")
+        for h, side in enumerate(("left", "right")):
+            hand = hands.get(side, hands.get("right" if side == "left" else "left"))
+            parts = [np.asarray(hand[k], dtype=np.float32).reshape(-1) for k in ("global_orient", "hand_pose", "shape", "trans")]
+            if parts[0].size != 3 or parts[1].size < ncomps or parts[2].size != 10 or parts[3].size != 3:
+                raise ValueError(f"annotation {a} ({side}): global_orient [3], hand_pose [>= {ncomps}], shape [10] and trans [3] expected")
+            parts[1] = parts[1][:ncomps]
+            out[a, h] = np.concatenate(parts)
+    return out
+
+
+def finish_metrics_s(state: dict) -> dict:
+    """The host-side end of a synthetic-set evaluation (evaluate.py:291-314).  state: host arrays of the device accumulator -- 'sums'
+    float64 [3, n], 'ce_num', 'ce_den' (floats), 'confusion' int64 [4, 4], 'ignored', per-window 'auc' float64 [3, >= W], 'l1',
+    'ce_num_w', 'ce_den_w' float64 [>= W], 'annotation' int32 [>= W], and 'n_frames' = W, 'stopped_at', 'status'.
+    -> the reference's dict ('pck3d', 'auc': same keys and nesting), then 'score' (the relative AUC evaluate_net returns second),
+    'segmentation', 'frames', 'n_frames', 'stopped_at'."""
+    status = int(state.get("status", _NO_WINDOW))
+    if status != _NO_WINDOW:
+        raise RuntimeError(f"window {status} could not be sampled: it is empty or has more unique pixels than the builder's `cap`")
+    W = int(state["n_frames"])
+    if W == 0:
+        raise RuntimeError("no frame was scored: nothing to average")
+    sums = np.asarray(state["sums"], dtype=np.float64)
+    pck = {"absolute": sums[0] / W, "relative": sums[1] / W, "right_root_relative": sums[2] / W}           # :291-293
+    auc = {"relative": round_auc_s(pck["relative"]), "absolute": round_auc_s(pck["absolute"]),
+           "right_root_relative": round_auc_s(pck["right_root_relative"])}                                 # :297-299
+    conf = np.asarray(state["confusion"], dtype=np.int64).reshape(4, 4).copy()
+    num, den = float(state["ce_num"]), float(state["ce_den"])
+    with np.errstate(divide="ignore", invalid="ignore"):
+        inter = np.diag(conf).astype(np.float64)
+        iou = inter / (conf.sum(0) + conf.sum(1) - np.diag(conf))          # NaN for a class that is neither labelled nor predicted
+    labelled = int(conf[1:].sum())
+    auc_f = np.asarray(state["auc"], dtype=np.float64)[:, :W]
+    nw, dw = np.asarray(state["ce_num_w"], dtype=np.float64)[:W], np.asarray(state["ce_den_w"], dtype=np.float64)[:W]
+    frames = {"absolute_auc": auc_f[0].copy(), "relative_auc": auc_f[1].copy(), "right_root_relative_auc": auc_f[2].copy(),
+              "l1": np.asarray(state["l1"], dtype=np.float64)[:W].copy(), "annotation": np.asarray(state["annotation"])[:W].copy(),
+              "loss_class_logits": np.divide(nw, dw, out=np.zeros(W), where=dw != 0)}
+    return {
+        "pck3d": pck, "auc": auc, "score": auc["relative"],
+        "segmentation": {"confusion": conf, "iou": iou, "accuracy": float(np.diag(conf)[1:].sum() / labelled) if labelled else 0.0,
+                         "loss_class_logits": num / den if den != 0 else 0.0, "ignored": int(state["ignored"])},
+        "frames": frames, "n_frames": W, "stopped_at": int(state["stopped_at"]),
+    }
+
+
+class AccumulatorS:
+    """The device state ev2h_eval_s_accumulate folds the batches of a synthetic-set evaluation into: ONE allocation, so that one copy
+    (`host()`) brings all of it back.  W: the number of windows it has room for."""
+
+    def __init__(self, device, W: int, num_steps: int):
+        if num_steps < 1 or W < 0:
+            raise ValueError("num_steps must be positive, W non-negative")
+        self.device, self.num_steps, self.cap_w = torch.device(device), int(num_steps), max(int(W), 1)
+        n, cap_w = self.num_steps + 1, self.cap_w
+        f64, i32, i64 = torch.float64, torch.int32, torch.int64
+        fields = [("sums", f64, (3 * n + 2,)), ("confusion", i64, (17,)), ("auc", f64, (3, cap_w)), ("l1", f64, (cap_w,)),
+                  ("ce_num_w", f64, (cap_w,)), ("ce_den_w", f64, (cap_w,)), ("annotation", i32, (cap_w,)), ("scalars", i32, (2,)), ("status", i32, (1,))]
+        self.layout, off = {}, 0
+        for name, dt, shape in fields:
+            nb = int(np.prod(shape)) * (4 if dt is i32 else 8)
+            self.layout[name] = (off, nb, dt, shape)
+            off += (nb + 7) // 8 * 8
+        self.blob = torch.zeros(off, device=self.device, dtype=torch.uint8)
+        self.device = self.blob.device                     # with its index, as the tensors handed to add() carry it
+        self.state = {k: self.blob[o:o + nb].view(dt).view(shape) for k, (o, nb, dt, shape) in self.layout.items()}
+        self.state["scalars"].copy_(torch.tensor([0, -1], dtype=torch.int32), non_blocking=False)
+        self.state["status"].fill_(_NO_WINDOW)
+
+    def add(self, pck, auc, l1, has_gt, annotation, confusion, ce_num, ce_den, ignored, window_ids, offset: int) -> None:
+        """One batch of B windows, the outputs of joint_metrics_f32_frames and segmentation_score, at positions offset .. offset + B - 1;
+        window_ids: contiguous int32 [B].  Device work only."""
+        B, dev, n = int(pck.shape[0]), self.device, self.num_steps + 1
+        if B < 1 or offset < 0 or offset + B > self.cap_w:
+            raise ValueError(f"windows {offset} .. {offset + B - 1} do not fit the accumulator's {self.cap_w}")
+        for t, name, dt, shape in ((pck, "pck", torch.float32, (B, 3, n)), (auc, "auc", torch.float64, (B, 3)), (l1, "l1", torch.float64, (B,)),
+                                   (has_gt, "has_gt", torch.int32, (B,)), (annotation, "annotation", torch.int32, (B,)),
+                                   (confusion, "confusion", torch.int32, (B, 4, 4)), (ce_num, "ce_num", torch.float64, (B,)),
+                                   (ce_den, "ce_den", torch.float64, (B,)), (ignored, "ignored", torch.int32, (B,)),
+                                   (window_ids, "window_ids", torch.int32, (B,))):
+            _dev_tensor(t, name, dt, shape, dev)
+        s = self.state
+        _lib.check(_lib.lib().ev2h_eval_s_accumulate(pck.data_ptr(), auc.data_ptr(), l1.data_ptr(), has_gt.data_ptr(), annotation.data_ptr(),
+                                                     confusion.data_ptr(), ce_num.data_ptr(), ce_den.data_ptr(), ignored.data_ptr(),
+                                                     window_ids.data_ptr(), B, self.num_steps, int(offset), self.cap_w, s["sums"].data_ptr(),
+                                                     s["confusion"].data_ptr(), s["auc"].data_ptr(), s["l1"].data_ptr(), s["ce_num_w"].data_ptr(),
+                                                     s["ce_den_w"].data_ptr(), s["annotation"].data_ptr(), s["scalars"].data_ptr(),
+                                                     _lib.stream_handle()), "ev2h_eval_s_accumulate")
+
+    def host(self) -> dict:
+        """The one device->host copy: the state as finish_metrics_s takes it."""
+        host = self.blob.cpu().numpy()
+        np_of = {torch.float64: np.float64, torch.int64: np.int64, torch.int32: np.int32}
+        st = {name: host[o:o + nb].view(np_of[dt]).reshape(shape) for name, (o, nb, dt, shape) in self.layout.items()}
+        n = self.num_steps + 1
+        return {"sums": st["sums"][:3 * n].reshape(3, n), "ce_num": float(st["sums"][3 * n]), "ce_den": float(st["sums"][3 * n + 1]),
+                "confusion": st["confusion"][:16].reshape(4, 4), "ignored": int(st["confusion"][16]), "auc": st["auc"], "l1": st["l1"],
+                "ce_num_w": st["ce_num_w"], "ce_den_w": st["ce_den_w"], "annotation": st["annotation"],
+                "n_frames": int(st["scalars"][0]), "stopped_at": int(st["scalars"][1]), "status": int(st["status"][0])}
+
+
+class SyntheticEvaluator:
+    """evaluate_net (evaluate.py:244-314) over the windows of a resident Ev2Hands-S event table, with the host out of the loop; per
+    batch of windows:
+
+        EventWindowBuilderS.accumulate_ranges -> sample_seeded (events and labels) -> seeded FPS start points -> forward ->
+        ev2h_joint_metrics_f32_frames against the hand layers' ground truth -> ev2h_segmentation_score -> ev2h_eval_s_accumulate
+
+    net: a TEHNetWrapper with the native hand layers.  Ground truth: `annotations` (the sequence's annotation dict, see
+    annotation_table; the joints of all A annotations come out of net.hands once, in begin()) or `joints` [A, 2, 21, 3] in metres
+    (the reference's mano_gt == 0 branch).  A window whose annotation index lies outside the table ends the evaluation there, as a
+    missing frame ends RecordingEvaluator's: `stopped_at` names it.
+    Window k's draws depend on (seed, k) only (RecordingEvaluator has the details): the result is bit for bit the same for every
+    batch size.  The draws are the project's own, not numpy's.
+    keep_outputs=True keeps per window, in `self.outputs`: 'j3d_left', 'j3d_right', 'class_logits' [W, 4, N], 'events' [W, 5, N],
+    'labels' [W, N], 'sample_idx' [W, N], 'fps_init' [4, W], 'pck' [W, 3, num_steps + 1], 'annotation' [W]."""
+
+    def __init__(self, net, annotations=None, *, joints=None, num_steps: int = 50, dist_max_mm: float = 50, seed: int = 0, batch: int = 256,
+                 n_events: int = 2048, keep_outputs: bool = False):
+        from .events import EventWindowBuilderS
+        self.net = net
+        self.device = next(net.parameters()).device
+        if self.device.type != "cuda":
+            raise RuntimeError("SyntheticEvaluator runs on the GPU only (there is no CPU fallback)")
+        if (annotations is None) == (joints is None):
+            raise ValueError("give either `annotations` or `joints`")
+        if num_steps < 1 or batch < 1 or n_events < 1 or not 0 <= int(seed) < 2 ** 64 or not 0 < float(dist_max_mm) < float("inf"):
+            raise ValueError("num_steps, batch and n_events must be positive, dist_max_mm positive and finite, seed an unsigned 64-bit integer")
+        if joints is not None:
+            j = joints if torch.is_tensor(joints) else torch.from_numpy(np.ascontiguousarray(joints))
+            if j.dim() != 4 or tuple(j.shape[1:]) != (2, 21, 3) or j.shape[0] < 1:
+                raise ValueError("joints must be [A, 2, 21, 3] (metres) with A >= 1")
+            self.joints, self.params = j.to(self.device, torch.float32).contiguous(), None
+        else:
+            self.joints = None
+            self.params = torch.from_numpy(annotation_table(annotations, net.net.n_pose_params)).to(self.device)
+        self.num_steps, self.dist_max_mm, self.seed, self.batch = int(num_steps), float(dist_max_mm), int(seed), int(batch)
+        self.keep_outputs = bool(keep_outputs)
+        self.builder = EventWindowBuilderS(self.device, n_events=n_events)
+        self.outputs = None
+        self._run = None
+
+    def ground_truth(self) -> torch.Tensor:
+        """float32 [A, 2, 21, 3] metres on the device: the given joints, or hands[side](...).joints of every annotation (:268-271)"""
+        if self.joints is not None:
+            return self.joints
+        p, nc = self.params, self.net.net.n_pose_params
+        per_hand = [self.net.hands[side](global_orient=p[:, h, :3], hand_pose=p[:, h, 3:3 + nc], betas=p[:, h, 3 + nc:13 + nc],
+                                         transl=p[:, h, 13 + nc:]).joints for h, side in enumerate(("left", "right"))]
+        return torch.stack(per_hand, 1).contiguous()
+
+    # ---- the three phases; evaluate() = begin + every step + finish --------------------------------------------------------
+    def begin(self, table, starts=None, stride: int | None = None, window_ids=None) -> int:
+        """Fix the windows (EventTableS.starts), compute the ground-truth joints, allocate every buffer of the loop and zero the
+        accumulator.  window_ids: the windows' numbers (default: their position in `starts`).  Returns the number of windows."""
+        dev, N, n = self.device, self.builder.n, self.num_steps + 1
+        host_starts = table.starts(starts, stride)
+        W = int(host_starts.shape[0])
+        B = max(1, min(self.batch, W))
+        if window_ids is None:
+            ids = torch.arange(W, device=dev, dtype=torch.int32)
+        else:
+            ids = torch.as_tensor(np.asarray(window_ids) if not torch.is_tensor(window_ids) else window_ids).to(dev, torch.int32).contiguous()
+            if tuple(ids.shape) != (W,):
+                raise ValueError("window_ids must hold one number per window")
+        f32, f64, i32, i64 = (dict(device=dev, dtype=t) for t in (torch.float32, torch.float64, torch.int32, torch.int64))
+        acc = AccumulatorS(dev, W, self.num_steps)
+        C, cap = self.net.net.in_channels, self.builder.cap
+        L = _lib.lib()
+        run = {
+            "table": table, "starts": torch.from_numpy(host_starts).to(dev), "ids": ids, "W": W, "acc": acc, "done": 0, "gt": self.ground_truth(),
+            "win": (torch.empty(B, cap, 8, **f32), torch.empty(B, **i32), torch.zeros(B, cap, **i32), torch.empty(B, **i32)),
+            "scratch": torch.empty(B, cap, 8, **f32),
+            "events": torch.empty(B, 5, N, **f32), "x": torch.empty(B, C, N, **f32) if C != 5 else None,
+            "labels": torch.empty(B, N, **i64), "idx": torch.empty(B, N, **i32) if self.keep_outputs else None,
+            "init": torch.empty(4 * B, device=dev, dtype=torch.long),
+            "rows": torch.empty(B, packed_width(N, self.net.net.n_pose_params), **f32),
+            "ws": torch.empty(L.ev2h_workspace_bytes(B, N), device=dev, dtype=torch.uint8),
+            "pck": torch.empty(B, 3, n, **f32), "aucb": torch.empty(B, 3, **f64), "l1": torch.empty(B, **f64), "has_gt": torch.empty(B, **i32),
+            "conf": torch.empty(B, 4, 4, **i32), "ce_num": torch.empty(B, **f64), "ce_den": torch.empty(B, **f64), "ignored": torch.empty(B, **i32),
+            "kept": {k: [] for k in ("j3d_left", "j3d_right", "class_logits", "events", "labels", "sample_idx", "fps_init", "pck", "annotation")},
+        }
+        self._run, self.outputs = run, None
+        if W and self.net.net.precision == "auto":
+            # the "auto" arithmetic decision compares two forwards on the host: take it now, on the first batch's own inputs, so
+            # that the loop itself stays free of host synchronisation
+            x, _, init = self._inputs(slice(0, min(B, W)))
+            self.net.net._auto_decide(x, self.net.hands, init)
+        self.net.net.packed(dev)
+        return W
+
+    def batches(self):
+        """index slices of at most `batch` windows each, in order"""
+        W = self._run["W"]
+        for i in range(0, W, self.batch):
+            yield slice(i, min(i + self.batch, W))
+
+    def _inputs(self, sl: slice):
+        """the network's input, the per-point labels and the seeded FPS start points of the windows starts[sl]"""
+        r = self._run
+        b = sl.stop - sl.start
+        ids = r["ids"][sl]
+        win = tuple(t[:b] for t in r["win"])
+        self.builder.accumulate_ranges(r["table"], r["starts"][sl], out=win, scratch=r["scratch"][:b])
+        sorted_t, counts, labels, _ = win
+        idx = r["idx"][:b] if r["idx"] is not None else False
+        res = self.builder.sample_seeded(sorted_t, counts, self.seed, ids, labels=labels, return_idx=idx, status=r["acc"].state["status"], out=r["events"][:b],
+                                         labels_out=r["labels"][:b])
+        events, lab = res[0], res[1]
+        init = TEHNet.seeded_fps_init(self.seed, ids, self.builder.n, out=r["init"][:4 * b].view(4, b))
+        if r["x"] is None:
+            x = events
+        else:
+            x = r["x"][:b]
+            x.copy_(events[:, :x.shape[1]])
+        return x, lab, init
+
+    def step(self, sl: slice) -> None:
+        """One batch: the windows starts[sl], sl.start = the number of windows done so far.  Device work only."""
+        r = self._run
+        if sl.start != r["done"] or not sl.start < sl.stop <= r["W"] or sl.stop - sl.start > r["events"].shape[0]:
+            raise ValueError("batches must follow each other in order and hold at most `batch` windows")
+        b = sl.stop - sl.start
+        x, lab, init = self._inputs(sl)
+        net = self.net.net
+        net.fps_init = init
+        with torch.no_grad():
+            out = net(x, self.net.hands, rows=r["rows"][:b], ws=r["ws"])
+        jl, jr, logits = out["left"]["j3d"], out["right"]["j3d"], out["class_logits"]      # views of the row matrix: read in place
+        annotation = r["win"][3][:b]
+        pck, aucb, l1, has_gt, conf, ce_num, ce_den, ignored = (r[k][:b] for k in ("pck", "aucb", "l1", "has_gt", "conf", "ce_num", "ce_den", "ignored"))
+        joint_metrics_f32_frames(jl, jr, r["gt"], annotation, self.num_steps, self.dist_max_mm, out=(pck, aucb, l1, has_gt))
+        segmentation_score(logits, lab, out=(conf, ce_num, ce_den, ignored))
+        r["acc"].add(pck, aucb, l1, has_gt, annotation, conf, ce_num, ce_den, ignored, r["ids"][sl], sl.start)
+        if self.keep_outputs:
+            k = r["kept"]
+            for name, t in (("j3d_left", jl), ("j3d_right", jr), ("class_logits", logits), ("events", r["events"][:b]), ("labels", lab),
+                            ("sample_idx", r["idx"][:b]), ("pck", pck), ("annotation", annotation)):
+                k[name].append(t.clone())
+            k["fps_init"].append(init.clone())
+        r["done"] = sl.stop
+
+    def finish(self) -> dict:
+        """The one device->host copy, then finish_metrics_s on the host."""
+        r = self._run
+        state = r["acc"].host()
+        if self.keep_outputs:
+            self.outputs = {k: torch.cat(v, 1 if k == "fps_init" else 0) for k, v in r["kept"].items() if v}
+        return finish_metrics_s(state)
+
+    def evaluate(self, table, starts=None, stride: int | None = None, window_ids=None) -> dict:
+        """table: ev2hands_amd.events.EventTableS; starts: the windows' first rows (an int, an array, or None for
+        range(0, E, stride)).  -> the metrics dict (finish_metrics_s)."""
+        self.begin(table, starts, stride, window_ids)
+        for sl in self.batches():
             self.step(sl)
         return self.finish()

@@ -87,7 +87,7 @@ class EventWindowBuilder:
                    "ev2h_event_window_sample")
         return out if labels is None else (out, lab)
 
-    def sample_seeded(self, table, counts, seed: int, window_ids, labels=None, return_idx: bool = False, status=None, out=None):
+    def sample_seeded(self, table, counts, seed: int, window_ids, labels=None, return_idx: bool = False, status=None, out=None, labels_out=None):
         """`sample` with the indices drawn on the device by a counter-based generator (csrc/random.hpp) instead of
         np.random.choice on the host: draw n of window window_ids[b] depends on (seed, window id, n) alone -- not on the batch the
         window is in, nor on any earlier draw -- and `counts` never leaves the device.  This is the project's own, opt-in draw; it is
@@ -95,7 +95,8 @@ class EventWindowBuilder:
         seed: 0 .. 2**64-1.  window_ids: contiguous device int32 [B].  status: device int32 [1] that the caller set to 2**31-1; it
         receives the smallest id of a window that could not be sampled (count outside [1, cap]; such a window's tensor is zeros).
         Without one, a fresh status is checked here, which costs a host synchronisation.  out: float32 [B, 5, N] to write into.
-        return_idx: True, or an int32 [B, N] device tensor that receives the drawn indices.
+        return_idx: True, or an int32 [B, N] device tensor that receives the drawn indices.  labels_out: int64 [B, N] to write the
+        labels into (with `labels`).
         -> events [B, 5, N] (, labels [B, N] int64 with `labels`) (, the indices [B, N] int32 with return_idx)."""
         B = int(table.shape[0])
         if window_ids.dtype != torch.int32 or window_ids.device != table.device or not window_ids.is_contiguous() or tuple(window_ids.shape) != (B,):
@@ -112,7 +113,11 @@ class EventWindowBuilder:
             out = torch.empty(B, 5, n, device=self.device, dtype=torch.float32)
         elif tuple(out.shape) != (B, 5, n) or out.dtype != torch.float32 or not out.is_contiguous():
             raise ValueError(f"out must be a contiguous float32 [{B}, 5, {n}] tensor")
-        lab = torch.empty(B, n, device=self.device, dtype=torch.int64) if labels is not None else None
+        lab = None
+        if labels is not None:
+            lab = torch.empty(B, n, device=self.device, dtype=torch.int64) if labels_out is None else labels_out
+            if tuple(lab.shape) != (B, n) or lab.dtype != torch.int64 or lab.device != table.device or not lab.is_contiguous():
+                raise ValueError(f"labels_out must be a contiguous int64 [{B}, {n}] device tensor")
         idx = torch.empty(B, n, device=self.device, dtype=torch.int32) if return_idx is True else (return_idx if torch.is_tensor(return_idx) else None)
         if B:
             _lib.check(_lib.lib().ev2h_event_window_sample_seeded(table.data_ptr(), counts.data_ptr(), self.cap, int(seed), window_ids.data_ptr(), B, n,
@@ -130,6 +135,39 @@ class EventWindowBuilder:
         return self.sample(table, counts, sample_idx)
 
 
+class EventTableS:
+    """The event table of a synthetic (Ev2Hands-S) sequence, resident on the device: `rows` [E, 6] (x, y, t_ns, p, annotation index,
+    event label), the `event` dataset of the reference's .h5 files (dataset/erpc.py:115-116,174-176), uploaded once as float64.
+    Item i of the reference's dataset is the window rows i .. min(i + n_events, E) - 1 (:170-174); windows at the table's end are
+    shorter.  Opening the .h5 / _anno.pickle files stays with the caller."""
+
+    ANNOTATION_COL, LABEL_COL = 4, 5
+
+    def __init__(self, device, rows):
+        self.device = torch.device(device)
+        ev = rows if torch.is_tensor(rows) else torch.from_numpy(np.ascontiguousarray(rows))
+        if ev.ndim != 2 or ev.shape[1] != 6 or ev.shape[0] < 1 or ev.shape[0] >= 2 ** 31:
+            raise ValueError("rows must be [E, 6] (x, y, t_ns, p, annotation index, event label) with 1 <= E < 2**31")
+        self.events = ev.to(self.device, torch.float64).contiguous()
+        self.n_rows, self.stride = int(ev.shape[0]), 6
+
+    def starts(self, starts=None, stride: int | None = None) -> np.ndarray:
+        """The windows' first rows as a host int32 array: an int, an array, or range(0, E, stride).  A start outside [0, E) raises."""
+        if starts is None:
+            if stride is None or int(stride) < 1:
+                raise ValueError("give `starts`, or a positive `stride` for range(0, E, stride)")
+            s = np.arange(0, self.n_rows, int(stride), dtype=np.int64)
+        else:
+            s = np.atleast_1d(np.asarray(starts))
+            if s.ndim != 1 or s.dtype.kind not in "iu":
+                raise ValueError("starts must be an int or a one-dimensional integer array")
+            s = s.astype(np.int64)
+        if s.size and (s.min() < 0 or s.max() >= self.n_rows):
+            bad = s[(s < 0) | (s >= self.n_rows)][0]
+            raise ValueError(f"window start {int(bad)} lies outside the table's rows [0, {self.n_rows})")
+        return s.astype(np.int32)
+
+
 class EventWindowBuilderS(EventWindowBuilder):
     """The synthetic-dataset (Ev2Hands-S) item builder, /root/reference/src/Ev2Hands/dataset/erpc.py:169-249 with augment off:
     windows are [n, 6] float64 tables (x, y, t_ns, p, annotation_index, event_label).  Timestamps are accumulated as they are,
@@ -140,6 +178,39 @@ class EventWindowBuilderS(EventWindowBuilder):
     def __init__(self, device, n_events: int = 2048, width: int = OUTPUT_WIDTH, height: int = OUTPUT_HEIGHT, cap: int = 4096):
         super().__init__(device, n_events, width, height, cap)
         self.raw_time = 1
+
+    def accumulate_ranges(self, table, starts, out=None, scratch=None):
+        """The sorted tables of `__call__` for windows cut on the device: window b = rows starts[b] .. min(starts[b] + n_events, E) - 1
+        of a resident EventTableS (starts: contiguous device int32 [B]; a start outside [0, E) gives an empty window, count 0 --
+        EventTableS.starts checks on the host).  Nothing is uploaded and nothing read back.
+        -> (sorted_table [B, cap, 8] f32, counts [B] i32, labels [B, cap] i32, annotation [B] i32): table rows, counts and labels
+        bit for bit those of `__call__` on the same windows cut on the host (self.table / self.table_labels), annotation = column 4
+        of each window's last row (erpc.py:200).  Draw with `sample_seeded(sorted_table, counts, seed, ids, labels=labels)`.
+        `out`: such a 4-tuple to write into (labels beyond a window's count are left as they are); `scratch`: float32 [B, cap, 8]
+        for the unsorted table."""
+        if not isinstance(table, EventTableS):
+            raise TypeError("EventWindowBuilderS.accumulate_ranges takes an EventTableS")
+        B = int(starts.shape[0])
+        if starts.dim() != 1 or starts.dtype != torch.int32 or not starts.is_contiguous() or starts.device != table.events.device:
+            raise ValueError("starts must be a contiguous int32 tensor [B] on the table's device")
+        dev = table.events.device
+        f32, i32 = dict(device=dev, dtype=torch.float32), dict(device=dev, dtype=torch.int32)
+        if out is None:
+            out = (torch.empty(B, self.cap, 8, **f32), torch.empty(B, **i32), torch.zeros(B, self.cap, **i32), torch.empty(B, **i32))
+        sorted_t, counts, labels, annotation = out
+        if scratch is None:
+            scratch = torch.empty(B, self.cap, 8, **f32)
+        for t, shape, dt, name in ((sorted_t, (B, self.cap, 8), torch.float32, "sorted table"), (scratch, (B, self.cap, 8), torch.float32, "scratch"),
+                                   (counts, (B,), torch.int32, "counts"), (labels, (B, self.cap), torch.int32, "labels"),
+                                   (annotation, (B,), torch.int32, "annotation")):
+            if tuple(t.shape) != shape or t.dtype != dt or t.device != dev or not t.is_contiguous():
+                raise ValueError(f"{name} must be a contiguous {dt} tensor {list(shape)} on {dev}")
+        if B:
+            _lib.check(_lib.lib().ev2h_event_window_build_s_ranges(table.events.data_ptr(), table.stride, table.n_rows, starts.data_ptr(), B, self.n,
+                                                                   self.w, self.h, self.cap, EventTableS.ANNOTATION_COL, EventTableS.LABEL_COL,
+                                                                   counts.data_ptr(), scratch.data_ptr(), sorted_t.data_ptr(), labels.data_ptr(),
+                                                                   annotation.data_ptr(), _lib.stream_handle()), "ev2h_event_window_build_s_ranges")
+        return sorted_t, counts, labels, annotation
 
     def __call__(self, windows, sampling: bool = True, sample_idx=None):
         B = len(windows)

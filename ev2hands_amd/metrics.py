@@ -58,3 +58,80 @@ def evaluate_joints_real_batch(j3d_left: torch.Tensor, j3d_right: torch.Tensor, 
                     "absolute_auc": round(auc_h[b, 0], 3), "relative_auc": round(auc_h[b, 1], 3),
                     "right_root_relative_auc": round(auc_h[b, 2], 3), "gt_index": int(best_h[b])})
     return out
+
+
+# ----------------------------------------------------------------------------- the synthetic test set's scorers (csrc/metrics_s.hip)
+def _dev_tensor(t, name, dtype, shape, dev=None, contiguous=True):
+    if not isinstance(t, torch.Tensor) or t.dtype != dtype or tuple(t.shape) != tuple(shape) or t.device.type != "cuda" \
+            or (dev is not None and t.device != dev) or (contiguous and not t.is_contiguous()):
+        raise ValueError(f"{name} must be a {'contiguous ' if contiguous else ''}{dtype} tensor {list(shape)} on "
+                         f"{dev if dev is not None else 'a CUDA device'}, got {getattr(t, 'dtype', type(t))} {list(getattr(t, 'shape', ()))} "
+                         f"on {getattr(t, 'device', None)}")
+
+
+def joint_metrics_f32_frames(j3d_left: torch.Tensor, j3d_right: torch.Tensor, joints_gt: torch.Tensor, annotation: torch.Tensor,
+                             num_steps: int = 50, dist_max_mm: float = 50.0, out=None):
+    """The three PCK curves as evaluate.py: evaluate_net computes them (:273-293 with :185-234), float32 throughout, for B windows on
+    the device (ev2h_joint_metrics_f32_frames).  j3d_left / j3d_right: float32 [B, 21, 3] metres, dense or the forward's strided views
+    (one common window stride, rows [21, 3] dense); joints_gt: contiguous float32 [A, 2, 21, 3] metres; annotation: contiguous int32
+    [B], window b is scored against row annotation[b] (outside [0, A): has_gt 0, zeros).  No host synchronisation.
+    -> (pck [B, 3, num_steps + 1] f32, auc [B, 3] f64 unrounded, l1 [B] f64 mean |pred - gt| in mm, has_gt [B] i32); `out`: such a
+    4-tuple to write into."""
+    if not isinstance(j3d_left, torch.Tensor) or j3d_left.dim() != 3 or j3d_left.shape[0] < 1:
+        raise ValueError("j3d_left must be a float32 [B, 21, 3] CUDA tensor with B >= 1")
+    B, dev = int(j3d_left.shape[0]), j3d_left.device
+    for name, t in (("j3d_left", j3d_left), ("j3d_right", j3d_right)):
+        _dev_tensor(t, name, torch.float32, (B, 21, 3), dev, contiguous=False)
+        if t.stride()[1:] != (3, 1) or (B > 1 and t.stride(0) < 63):
+            raise ValueError(f"{name}: each window's [21, 3] block must be dense and the windows must not overlap, got strides {t.stride()}")
+    stride = int(j3d_left.stride(0)) if B > 1 else 63
+    if B > 1 and int(j3d_right.stride(0)) != stride:
+        raise ValueError("j3d_left and j3d_right must have the same window stride")
+    if not isinstance(joints_gt, torch.Tensor) or joints_gt.dim() != 4 or joints_gt.shape[0] < 1:
+        raise ValueError("joints_gt must be a float32 [A, 2, 21, 3] CUDA tensor with A >= 1")
+    _dev_tensor(joints_gt, "joints_gt", torch.float32, (int(joints_gt.shape[0]), 2, 21, 3), dev)
+    _dev_tensor(annotation, "annotation", torch.int32, (B,), dev)
+    if int(num_steps) != num_steps or num_steps < 1:
+        raise ValueError(f"num_steps must be an integer >= 1, got {num_steps!r}")
+    if not (0.0 < float(dist_max_mm) < float("inf")):
+        raise ValueError(f"dist_max_mm must be positive and finite, got {dist_max_mm!r}")
+    n = int(num_steps) + 1
+    if out is None:
+        out = (torch.empty(B, 3, n, device=dev, dtype=torch.float32), torch.empty(B, 3, device=dev, dtype=torch.float64),
+               torch.empty(B, device=dev, dtype=torch.float64), torch.empty(B, device=dev, dtype=torch.int32))
+    pck, auc, l1, has_gt = out
+    _dev_tensor(pck, "pck", torch.float32, (B, 3, n), dev)
+    _dev_tensor(auc, "auc", torch.float64, (B, 3), dev)
+    _dev_tensor(l1, "l1", torch.float64, (B,), dev)
+    _dev_tensor(has_gt, "has_gt", torch.int32, (B,), dev)
+    _lib.check(_lib.lib().ev2h_joint_metrics_f32_frames(j3d_left.data_ptr(), j3d_right.data_ptr(), stride, joints_gt.data_ptr(), int(joints_gt.shape[0]),
+                                                        annotation.data_ptr(), B, int(num_steps), float(dist_max_mm), pck.data_ptr(), auc.data_ptr(),
+                                                        l1.data_ptr(), has_gt.data_ptr(), _lib.stream_handle()), "ev2h_joint_metrics_f32_frames")
+    return pck, auc, l1, has_gt
+
+
+def segmentation_score(class_logits: torch.Tensor, labels: torch.Tensor, out=None):
+    """A segmentation scored against per-point labels on the device (ev2h_segmentation_score).  class_logits: float32 [B, 4, N], dense
+    or the forward's strided view (classes N apart, points dense); labels: contiguous int64 [B, N].
+    -> (confusion [B, 4, 4] i32 (label, prediction; first maximum, NaN = maximum, as torch.argmax), ce_num [B], ce_den [B] f64: the
+    two sums of the weighted cross-entropy of losses.py:203 (weights [1, 30, 30, 10], ignore_index 0), ignored [B] i32: labels
+    outside 0..3).  `out`: such a 4-tuple to write into.  No host synchronisation."""
+    if not isinstance(class_logits, torch.Tensor) or class_logits.dim() != 3 or class_logits.shape[0] < 1 or class_logits.shape[2] < 1:
+        raise ValueError("class_logits must be a float32 [B, 4, N] CUDA tensor with B, N >= 1")
+    B, N, dev = int(class_logits.shape[0]), int(class_logits.shape[2]), class_logits.device
+    _dev_tensor(class_logits, "class_logits", torch.float32, (B, 4, N), dev, contiguous=False)
+    if class_logits.stride()[1:] != (N, 1) or (B > 1 and class_logits.stride(0) < 4 * N):
+        raise ValueError(f"class_logits: each window's [4, N] block must be dense and the windows must not overlap, got strides {class_logits.stride()}")
+    stride = int(class_logits.stride(0)) if B > 1 else 4 * N
+    _dev_tensor(labels, "labels", torch.int64, (B, N), dev)
+    if out is None:
+        out = (torch.empty(B, 4, 4, device=dev, dtype=torch.int32), torch.empty(B, device=dev, dtype=torch.float64),
+               torch.empty(B, device=dev, dtype=torch.float64), torch.empty(B, device=dev, dtype=torch.int32))
+    conf, num, den, ignored = out
+    _dev_tensor(conf, "confusion", torch.int32, (B, 4, 4), dev)
+    _dev_tensor(num, "ce_num", torch.float64, (B,), dev)
+    _dev_tensor(den, "ce_den", torch.float64, (B,), dev)
+    _dev_tensor(ignored, "ignored", torch.int32, (B,), dev)
+    _lib.check(_lib.lib().ev2h_segmentation_score(class_logits.data_ptr(), stride, labels.data_ptr(), B, N, conf.data_ptr(), num.data_ptr(),
+                                                  den.data_ptr(), ignored.data_ptr(), _lib.stream_handle()), "ev2h_segmentation_score")
+    return conf, num, den, ignored

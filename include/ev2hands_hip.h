@@ -410,6 +410,17 @@ int ev2h_event_window_build(const double* events, int ev_stride, const int32_t* 
 int ev2h_event_window_timesort(const float* uniq_in, const int32_t* uniq_count, int cap, const double* events, int ev_stride,
                                int label_col, const int32_t* offsets, int B, float* uniq_out, int32_t* labels_out,
                                ev2h_stream_t stream);
+/* Ev2Hands-S windows cut on the device from a RESIDENT table (erpc.py:170-211): n_rows device float64 rows of ev_stride columns (x, y,
+ * t_ns, p, annotation index, event label), window b = rows starts[b] .. min(starts[b] + n_events, n_rows) - 1 (windows at the
+ * table's end are shorter; a start outside [0, n_rows) is an empty window: count 0, annotation -1).  ev2h_event_window_build with
+ * raw_time = 1 followed by ev2h_event_window_timesort, reading the table in place: uniq_sorted [B][cap][8], uniq_count [B] and
+ * labels [B][cap] (rows below min(M, cap)) are bit for bit those of the two calls on host-cut windows.  annotation [B] = column
+ * anno_col of the window's LAST row (:200).  uniq_scratch [B][cap][8] holds the unsorted table in between.  n_events <= 32768,
+ * cap <= 16384.  Two launches, no host synchronisation, capturable. */
+int ev2h_event_window_build_s_ranges(const double* events, int ev_stride, int n_rows, const int32_t* starts, int B, int n_events,
+                                     int width, int height, int cap, int anno_col, int label_col, int32_t* uniq_count,
+                                     float* uniq_scratch, float* uniq_sorted, int32_t* labels, int32_t* annotation,
+                                     ev2h_stream_t stream);
 /* Resampling + pc_normalize: sample_idx [B][N] int32 (the reference draws them with np.random.choice on the host; for erpc.py's
  * sampling=False branch pass arange(M) followed by the N - M drawn indices) -> out_cm [B][5][N] float32 = (x, y, t, pos_cnt,
  * neg_cnt), the hot path's input.  uniq_labels [B][cap] / out_labels [B][N] int64 optional (Ev2Hands-S 'class_logits' target). */
@@ -541,6 +552,40 @@ int ev2h_eval_accumulate(const float* pck, const double* auc, const double* mpjp
                          int offset, int w_cap, double* sums, double* frame_joint_loss, double* frame_root_distance,
                          double* frame_auc, int32_t* frame_collisions, int32_t* frame_frame_index, int32_t* scalars,
                          ev2h_stream_t stream);
+
+/* ---- a synthetic test set's scores, accumulated on the device (evaluate.py:185-314: evaluate_net; losses.py:203) ------------------- */
+/* The three PCK curves of evaluate.py:185-234 as evaluate_net executes them -- NOT ev2h_joint_metrics' arithmetic: predictions
+ * (window b at j3d_* + b * pred_stride floats, [21][3] metres; pred_stride 0 = dense, else >= 63) and ground truth (joints_gt
+ * [A][2][21][3] float32 metres, row annotation[b]) are both float32, `* 1000`, the root subtractions and the differences are
+ * float32 operations, and the distance is torch.norm's on float32: sqrtf(fmaf(z, z, fmaf(y, y, x * x))).  Thresholds
+ * (float)((dist_max_mm / num_steps) * s), strict <, values k / 42 in float32.  pck [B][3][num_steps + 1] (absolute, relative,
+ * right-root-relative), auc [B][3] the unrounded trapezoid / (num_steps + 1), l1 [B] = mean |pred - gt| in mm over the 126
+ * coordinates (float64 sum of the float32 differences; the reference prints it per batch, :289).  has_gt [B] = 0 where
+ * annotation[b] lies outside [0, A): that window's outputs are zeros and nothing of joints_gt is read. */
+int ev2h_joint_metrics_f32_frames(const float* j3d_left, const float* j3d_right, size_t pred_stride, const float* joints_gt, int A,
+                                  const int32_t* annotation, int B, int num_steps, double dist_max_mm, float* pck, double* auc,
+                                  double* l1, int32_t* has_gt, ev2h_stream_t stream);
+/* A segmentation scored against per-point labels (the project's own: evaluate_net scores none).  class_logits: window b at
+ * + b * logits_stride floats (0 = 4 * N), [4][N] float32; labels [B][N] int64; N any positive number.  Per window: confusion
+ * [B][4][4] int32 (label, prediction), prediction = the first maximum of the four logits, a NaN counting as the maximum
+ * (torch.argmax); the two sums of the reference's segmentation loss (losses.py:203: class weights [1, 30, 30, 10], ignore_index 0)
+ * ce_num [B] = sum of w_y * (logsumexp(x) - x_y) and ce_den [B] = sum of w_y over the points with label 1..3, in float64 (a window
+ * without such a point has 0 and 0); ignored [B] = points whose label lies outside 0..3, which are counted nowhere else. */
+int ev2h_segmentation_score(const float* class_logits, size_t logits_stride, const int64_t* labels, int B, int N, int32_t* confusion,
+                            double* ce_num, double* ce_den, int32_t* ignored, ev2h_stream_t stream);
+/* ev2h_eval_accumulate for the two scorers above.  State, zeroed before the first call except scalars = (0, -1):
+ *   sums [3 * (num_steps + 1) + 2] float64: the three PCK curves summed over the windows, then ce_num and ce_den;
+ *   conf_total [17] int64: the confusion matrix, then `ignored`;
+ *   frame_auc [3][w_cap], frame_l1, frame_ce_num, frame_ce_den [w_cap] float64, frame_annotation [w_cap] int32: this batch's
+ *   windows at positions offset .. offset + B - 1;  scalars [2] int32: windows scored, and stopped_at = the id of the first window
+ *   without ground truth, -1 if none.
+ * Windows at or behind the first one with has_gt = 0, in this or an earlier call, are not accumulated.  Every total is added in
+ * window order by one thread: it equals a sequential loop over the windows bit for bit, whatever the batch size. */
+int ev2h_eval_s_accumulate(const float* pck, const double* auc, const double* l1, const int32_t* has_gt, const int32_t* annotation,
+                           const int32_t* confusion, const double* ce_num, const double* ce_den, const int32_t* ignored,
+                           const int32_t* window_ids, int B, int num_steps, int offset, int w_cap, double* sums, int64_t* conf_total,
+                           double* frame_auc, double* frame_l1, double* frame_ce_num, double* frame_ce_den,
+                           int32_t* frame_annotation, int32_t* scalars, ev2h_stream_t stream);
 
 /* ---- two-hand mesh self-collision (next row 8f-4; evaluate_ev2hands_r.py:128-160, utils/__init__.py:106-124) ---------------- */
 /* verts_left / verts_right [B][nv][3] float32 metres (the forward's vertices), faces [nf][3] int32 (nv <= 778, nf <= 1538).
