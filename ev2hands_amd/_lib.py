@@ -79,6 +79,11 @@ class TensorDesc(C.Structure):
 
 
 DT_F32, DT_F64, DT_I64 = 0, 1, 2
+# EV2H_LOSS_*: slots of ev2h_loss_terms' rows and the length of ev2h_loss_accumulate's state
+LOSS_INTER_SHAPE, LOSS_INTER_TRANSL, LOSS_INTER_J3D, LOSS_HAND, LOSS_PER_HAND = 0, 1, 2, 3, 9
+LOSS_H_GLOBAL_ORIENT, LOSS_H_HAND_POSE, LOSS_H_SHAPE, LOSS_H_RJ3D, LOSS_H_J3D, LOSS_H_TRANSL, LOSS_H_REG_BETAS, LOSS_H_REG_POSE, LOSS_H_J2D = range(9)
+LOSS_NT = LOSS_HAND + 2 * LOSS_PER_HAND
+LOSS_NSTATE = LOSS_NT + 6
 PACK_EQUALIZE, PACK_HOST_ONLY, PACK_UNEQUALIZED_OK = 1, 2, 4
 FAM_SA, FAM_ROWS, FAM_QCONV, FAM_DENSE, FAM_ALL = 1, 2, 4, 8, 15      # EV2H_FAM_*: kernel families of the "f16" mode (ev2h_weights.f16_families)
 
@@ -91,7 +96,8 @@ W_EQUALIZED, W_UNEQUALIZED_OK = 1, 2
 # signature changed -- so the version stays 8.  The same holds for the recording exports (ev2h_event_stream_*, ev2h_event_window_build_ranges)
 # and for the seeded-draw / recording-evaluation exports (ev2h_event_window_sample_seeded, ev2h_fps_init_seeded, ev2h_joint_metrics_frames,
 # ev2h_eval_accumulate), and for ev2h_events_undistort, and for the synthetic-set evaluation exports (ev2h_event_window_build_s_ranges,
-# ev2h_joint_metrics_f32_frames, ev2h_segmentation_score, ev2h_eval_s_accumulate).
+# ev2h_joint_metrics_f32_frames, ev2h_segmentation_score, ev2h_eval_s_accumulate), and for the loss exports (ev2h_loss_terms,
+# ev2h_loss_accumulate).
 ABI_VERSION = 8     # 8: EV2H_PREC_F16 (one fp16 plane with f16x2's range machinery); 3: F16X2 range records; 4: ev2h_fp_mlp, ev2h_weights.fp1m; 5: window strides of the outputs; 6: ev2h_pack_weights, ev2h_weights.flags; 7: ev2h_sa_desc.xyz_out
 
 PREC = {"f32": 0, "bf16": 1, "f16x2": 2, "bf16x3": 3, "f16": 4}
@@ -123,6 +129,7 @@ EXPORTS = [
     "ev2h_event_window_sample_seeded", "ev2h_fps_init_seeded", "ev2h_joint_metrics_frames", "ev2h_eval_accumulate",
     "ev2h_events_undistort",
     "ev2h_event_window_build_s_ranges", "ev2h_joint_metrics_f32_frames", "ev2h_segmentation_score", "ev2h_eval_s_accumulate",
+    "ev2h_loss_terms", "ev2h_loss_accumulate",
 ]
 
 _lib = None
@@ -213,6 +220,9 @@ def lib() -> C.CDLL:
     L.ev2h_joint_metrics_f32_frames.argtypes = [vp, vp, C.c_size_t, vp, ci, vp, ci, ci, C.c_double, vp, vp, vp, vp, vp]
     L.ev2h_segmentation_score.argtypes = [vp, C.c_size_t, vp, ci, ci, vp, vp, vp, vp, vp]
     L.ev2h_eval_s_accumulate.argtypes = [vp] * 10 + [ci] * 4 + [vp] * 8 + [vp]
+    L.ev2h_loss_terms.argtypes = [vp, vp, C.c_size_t, vp, vp, C.c_size_t, ci, ci, vp, vp, vp, C.c_size_t, vp, ci, vp, ci, C.POINTER(C.c_float),
+                                  C.c_float, C.c_float, vp, vp, vp, vp]
+    L.ev2h_loss_accumulate.argtypes = [vp, vp, vp, vp, vp, ci, vp, vp, vp]
     L.ev2h_event_window_pixels.argtypes = [vp, vp, ci, vp, ci, ci, vp, vp, vp, vp]
     L.ev2h_demo_point_panels.argtypes = [vp, vp, vp, vp, C.c_size_t, ci, ci, ci, ci, vp, ci, ci, ci, vp]
     L.ev2h_render_scratch_bytes.restype = C.c_size_t

@@ -31,20 +31,27 @@ def device_faces(faces, dev) -> torch.Tensor:
 
 
 def mesh_collisions(verts_left: torch.Tensor, verts_right: torch.Tensor, faces_left, faces_right, max_pairs: int = 0,
-                    scale: float = 1000.0, max_per_triangle: int = 0, scratch: torch.Tensor | None = None):
+                    scale: float = 1000.0, max_per_triangle: int = 0, scratch: torch.Tensor | None = None, out=None):
     """verts_* [B,nv,3] float32 metres on the GPU, faces_* [nf,3] (ndarray or tensor).  Returns (counts [B] int32 tensor,
     pairs [B,max_pairs,2] int32 tensor or None; rows past counts[b] are unspecified).  max_per_triangle: the BVH's
     `max_collisions` cap (0 = none), see ev2h_mesh_collisions.  scratch: optional caller-owned uint8 buffer of at least
     `ev2h_mesh_collisions_scratch_bytes(B, nf)` bytes, used on the CURRENT stream only (the phases of one search communicate
-    through it); without one a buffer cached per (device, stream) is used."""
+    through it); without one a buffer cached per (device, stream) is used.  out: optional (counts [B] int32, pairs [B, max_pairs, 2]
+    int32 or None) to write into instead of new tensors."""
     B, nv, _ = verts_left.shape
     dev = verts_left.device
     vl = verts_left.to(torch.float32).contiguous()
     vr = verts_right.to(dev, torch.float32).contiguous()
     fl, fr = _faces(faces_left, dev), _faces(faces_right, dev)
     nf = fl.shape[0]
-    counts = torch.empty(B, device=dev, dtype=torch.int32)
-    pairs = torch.empty(B, max_pairs, 2, device=dev, dtype=torch.int32) if max_pairs > 0 else None
+    if out is not None:
+        counts, pairs = out
+        if counts.dtype != torch.int32 or tuple(counts.shape) != (B,) or counts.device != dev or not counts.is_contiguous() or (max_pairs > 0 and (
+                pairs is None or pairs.dtype != torch.int32 or tuple(pairs.shape) != (B, max_pairs, 2) or pairs.device != dev or not pairs.is_contiguous())):
+            raise ValueError("mesh_collisions: out must be (counts [B] int32, pairs [B, max_pairs, 2] int32), contiguous, on the vertices' device")
+    else:
+        counts = torch.empty(B, device=dev, dtype=torch.int32)
+        pairs = torch.empty(B, max_pairs, 2, device=dev, dtype=torch.int32) if max_pairs > 0 else None
     L = _lib.lib()
     # a scratch buffer lets the library split a window's row blocks over two workgroups when the batch alone cannot fill the chip
     if scratch is None and B <= 128:
@@ -124,20 +131,40 @@ class CollisionLoss:
             raise ValueError("an uncapped pair search (max_collisions = 0) needs an explicit max_pairs")
         return 2 * nf * self.max_collisions
 
-    def per_window(self, outs, faces=None) -> torch.Tensor:
+    def workspace(self, B: int, nv: int, nf: int, device) -> dict:
+        """Every buffer per_window needs for up to B windows, allocated once: pass it as `work` and a call allocates nothing."""
+        cap = self.capacity(nf)
+        i32 = dict(device=device, dtype=torch.int32)
+        nbytes = _lib.lib().ev2h_mesh_collisions_scratch_bytes(B, nf) if B <= 128 else 0
+        return {"verts": (torch.empty(B, nv, 3, device=device), torch.empty(B, nv, 3, device=device)), "counts": torch.empty(B, **i32),
+                "pairs": torch.empty(B, cap, 2, **i32), "loss": torch.empty(B, device=device, dtype=torch.float64),
+                "scratch": torch.empty(nbytes, device=device, dtype=torch.uint8) if nbytes else None}
+
+    def per_window(self, outs, faces=None, work=None) -> torch.Tensor:
         """[B] float64 penalties.  faces: optional (faces_left, faces_right) overriding outs[side]['faces'] (e.g. device_faces()
-        tensors prepared once)."""
+        tensors prepared once).  work: optional buffers of `workspace()` (B at most theirs): the result is a view of work['loss']."""
         vl, vr = outs["left"]["vertices"], outs["right"]["vertices"]
         dev = vl.device
+        if work is not None:
+            b = vl.shape[0]
+            wl, wr = work["verts"][0][:b], work["verts"][1][:b]
+            wl.copy_(vl)
+            wr.copy_(vr)
+            vl, vr = wl, wr
         fl, fr = faces if faces is not None else (outs["left"]["faces"], outs["right"]["faces"])
         flt, frt = self._device_faces(fl, fr, dev)
         if self.reference_batch_quirk:
             vl, vr = vl[:1].expand_as(vl), vr[:1].expand_as(vr)                          # losses.py:88-93: every item reads item 0
         cap = self.capacity(flt.shape[0])
-        counts, pairs = mesh_collisions(vl, vr, flt, frt, max_pairs=cap, scale=1.0, max_per_triangle=self.max_collisions)
-        self.last_counts = counts
         B, nv, _ = vl.shape
-        loss = torch.zeros(B, device=dev, dtype=torch.float64)
+        if work is not None:
+            counts, pairs = mesh_collisions(vl, vr, flt, frt, max_pairs=cap, scale=1.0, max_per_triangle=self.max_collisions, scratch=work["scratch"],
+                                            out=(work["counts"][:B], work["pairs"][:B]))
+            loss = work["loss"][:B].zero_()
+        else:
+            counts, pairs = mesh_collisions(vl, vr, flt, frt, max_pairs=cap, scale=1.0, max_per_triangle=self.max_collisions)
+            loss = torch.zeros(B, device=dev, dtype=torch.float64)
+        self.last_counts = counts
         vlc, vrc = vl.to(torch.float32).contiguous(), vr.to(dev, torch.float32).contiguous()
         _lib.check(_lib.lib().ev2h_collision_penalty(vlc.data_ptr(), vrc.data_ptr(),
                                                      flt.data_ptr(), frt.data_ptr(), B, nv, flt.shape[0], 1.0, float(self.sigma),

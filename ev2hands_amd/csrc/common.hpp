@@ -86,6 +86,16 @@ __device__ __forceinline__ float wave_sum_f32(float v) {
     return v;
 }
 
+// float64 sum over the wavefront in a fixed order (xor butterfly: every lane ends with the same bits)
+__device__ __forceinline__ double wave_sum_f64(double v) {
+#pragma unroll
+    for (int o = 32; o >= 1; o >>= 1) {
+        const int lo = __shfl_xor(__double2loint(v), o, 64), hi = __shfl_xor(__double2hiint(v), o, 64);
+        v += __hiloint2double(hi, lo);
+    }
+    return v;
+}
+
 // wave-wide unsigned max with DPP row shifts / row broadcasts (6 short-latency steps instead of 6 ds_bpermute round trips);
 // result broadcast from lane 63
 __device__ __forceinline__ unsigned wave_max_u32_dpp(unsigned v) {

@@ -24,15 +24,6 @@ struct MetSP {
     int32_t* has_gt;                           // [B]
 };
 
-__device__ __forceinline__ double wave_sum_f64_s(double v) {
-#pragma unroll
-    for (int o = 32; o >= 1; o >>= 1) {
-        const int lo = __shfl_xor(__double2loint(v), o, 64), hi = __shfl_xor(__double2hiint(v), o, 64);
-        v += __hiloint2double(hi, lo);
-    }
-    return v;
-}
-
 // torch.norm(p=2, dim=1) on a float32 [42, 3] tensor, as the CPU kernel evaluates it: sqrt(fma(z, z, fma(y, y, x * x))), every step
 // rounded to float32.  NOT (x*x + y*y) + z*z: the two differ in the last bit for about one vector in nine, which moves a joint
 // across a threshold it sits on.
@@ -91,7 +82,7 @@ __global__ __launch_bounds__(64) void joint_metrics_f32_frames_kernel(MetSP p) {
     }
     // "L1 Distance" (:289), per window: mean |pred - gt| over the 126 coordinates, the float32 differences summed in float64
     const double l = act ? ((double)fabsf(ax) + (double)fabsf(ay)) + (double)fabsf(az) : 0.0;
-    const double tot = wave_sum_f64_s(l);
+    const double tot = wave_sum_f64(l);
     if (lane == 0) { p.l1[b] = tot / 126.0; p.has_gt[b] = 1; }
 }
 

@@ -30,8 +30,8 @@ from __future__ import annotations
 import numpy as np
 import torch
 
-from . import _lib, synth
-from .collision import device_faces
+from . import _lib, losses as _losses, synth
+from .collision import CollisionLoss, device_faces
 from .dist import packed_width
 from .events import EventWindowBuilder
 from .metrics import _dev_tensor, joint_metrics_f32_frames, segmentation_score
@@ -291,6 +291,28 @@ def annotation_table(annotations, ncomps: int = synth.MANO_CMPS) -> np.ndarray:
     return out
 
 
+def annotation_flags(annotations, reference_quirks: bool = True) -> np.ndarray:
+    """The `valid` and `handedness` Ev2HandSDataset.__getitem__ attaches to annotation_table's rows (dataset/erpc.py:266-294), int32
+    [A, 2, 2]: per hand (valid, handedness), hand 0 = left.  Both hands present: (1, 1) each.  One hand missing: its handedness is 0,
+    the present one's 1 -- and, upstream, `hand_data['left'] = hand_data['right']` (:285, :290) makes both entries ONE dict, so the
+    `['valid'] = False` that follows clears the valid of BOTH hands: reference_quirks=True restates that (a one-hand annotation masks
+    every per-hand term of the loss); reference_quirks=False keeps the present hand valid."""
+    items = dict(enumerate(annotations)) if isinstance(annotations, (list, tuple)) else dict(annotations)
+    keys = sorted(int(k) for k in items)
+    if not keys or keys != list(range(len(keys))) or any(int(k) != k for k in items):
+        raise ValueError("the annotation indices must be exactly 0 .. A-1")
+    items = {int(k): v for k, v in items.items()}
+    out = np.zeros((len(keys), 2, 2), dtype=np.int32)
+    for a in keys:
+        present = [side in items[a] for side in ("left", "right")]
+        if not any(present):
+            raise ValueError(f"annotation {a} has neither hand")
+        for h in range(2):
+            out[a, h, 1] = int(present[h])
+            out[a, h, 0] = int(all(present)) if reference_quirks else int(present[h])
+    return out
+
+
 def finish_metrics_s(state: dict) -> dict:
     """The host-side end of a synthetic-set evaluation (evaluate.py:291-314).  state: host arrays of the device accumulator -- 'sums'
     float64 [3, n], 'ce_num', 'ce_den' (floats), 'confusion' int64 [4, 4], 'ignored', per-window 'auc' float64 [3, >= W], 'l1',
@@ -328,9 +350,10 @@ def finish_metrics_s(state: dict) -> dict:
 
 class AccumulatorS:
     """The device state ev2h_eval_s_accumulate folds the batches of a synthetic-set evaluation into: ONE allocation, so that one copy
-    (`host()`) brings all of it back.  W: the number of windows it has room for."""
+    (`host()`) brings all of it back.  W: the number of windows it has room for.  loss_state=True adds ev2h_loss_accumulate's state
+    ('loss_state' float64 [NSTATE], 'loss_scalars' int32 (0, -1)) to the same allocation."""
 
-    def __init__(self, device, W: int, num_steps: int):
+    def __init__(self, device, W: int, num_steps: int, loss_state: bool = False):
         if num_steps < 1 or W < 0:
             raise ValueError("num_steps must be positive, W non-negative")
         self.device, self.num_steps, self.cap_w = torch.device(device), int(num_steps), max(int(W), 1)
@@ -338,6 +361,8 @@ class AccumulatorS:
         f64, i32, i64 = torch.float64, torch.int32, torch.int64
         fields = [("sums", f64, (3 * n + 2,)), ("confusion", i64, (17,)), ("auc", f64, (3, cap_w)), ("l1", f64, (cap_w,)),
                   ("ce_num_w", f64, (cap_w,)), ("ce_den_w", f64, (cap_w,)), ("annotation", i32, (cap_w,)), ("scalars", i32, (2,)), ("status", i32, (1,))]
+        if loss_state:
+            fields += [("loss_state", f64, (_lib.LOSS_NSTATE,)), ("loss_scalars", i32, (2,))]
         self.layout, off = {}, 0
         for name, dt, shape in fields:
             nb = int(np.prod(shape)) * (4 if dt is i32 else 8)
@@ -347,6 +372,8 @@ class AccumulatorS:
         self.device = self.blob.device                     # with its index, as the tensors handed to add() carry it
         self.state = {k: self.blob[o:o + nb].view(dt).view(shape) for k, (o, nb, dt, shape) in self.layout.items()}
         self.state["scalars"].copy_(torch.tensor([0, -1], dtype=torch.int32), non_blocking=False)
+        if loss_state:
+            self.state["loss_scalars"].copy_(self.state["scalars"])
         self.state["status"].fill_(_NO_WINDOW)
 
     def add(self, pck, auc, l1, has_gt, annotation, confusion, ce_num, ce_den, ignored, window_ids, offset: int) -> None:
@@ -375,10 +402,13 @@ class AccumulatorS:
         np_of = {torch.float64: np.float64, torch.int64: np.int64, torch.int32: np.int32}
         st = {name: host[o:o + nb].view(np_of[dt]).reshape(shape) for name, (o, nb, dt, shape) in self.layout.items()}
         n = self.num_steps + 1
-        return {"sums": st["sums"][:3 * n].reshape(3, n), "ce_num": float(st["sums"][3 * n]), "ce_den": float(st["sums"][3 * n + 1]),
-                "confusion": st["confusion"][:16].reshape(4, 4), "ignored": int(st["confusion"][16]), "auc": st["auc"], "l1": st["l1"],
-                "ce_num_w": st["ce_num_w"], "ce_den_w": st["ce_den_w"], "annotation": st["annotation"],
-                "n_frames": int(st["scalars"][0]), "stopped_at": int(st["scalars"][1]), "status": int(st["status"][0])}
+        out = {"sums": st["sums"][:3 * n].reshape(3, n), "ce_num": float(st["sums"][3 * n]), "ce_den": float(st["sums"][3 * n + 1]),
+               "confusion": st["confusion"][:16].reshape(4, 4), "ignored": int(st["confusion"][16]), "auc": st["auc"], "l1": st["l1"],
+               "ce_num_w": st["ce_num_w"], "ce_den_w": st["ce_den_w"], "annotation": st["annotation"],
+               "n_frames": int(st["scalars"][0]), "stopped_at": int(st["scalars"][1]), "status": int(st["status"][0])}
+        if "loss_state" in st:
+            out["loss_state"], out["loss_scalars"] = st["loss_state"], st["loss_scalars"]
+        return out
 
 
 class SyntheticEvaluator:
@@ -395,10 +425,16 @@ class SyntheticEvaluator:
     Window k's draws depend on (seed, k) only (RecordingEvaluator has the details): the result is bit for bit the same for every
     batch size.  The draws are the project's own, not numpy's.
     keep_outputs=True keeps per window, in `self.outputs`: 'j3d_left', 'j3d_right', 'class_logits' [W, 4, N], 'events' [W, 5, N],
-    'labels' [W, N], 'sample_idx' [W, N], 'fps_init' [4, W], 'pck' [W, 3, num_steps + 1], 'annotation' [W]."""
+    'labels' [W, N], 'sample_idx' [W, N], 'fps_init' [4, W], 'pck' [W, 3, num_steps + 1], 'annotation' [W]; with losses=True also
+    'params_left', 'params_right' [W, 16 + n_pose], 'vertices_left', 'vertices_right' [W, 778, 3].
+    losses=True (needs `annotations`) adds the reference's training loss over the evaluated set (losses.py: Loss, mano branch; see
+    ev2hands_amd/losses.py): per batch ev2h_loss_terms against the annotation tables, CollisionLoss.per_window and
+    ev2h_loss_accumulate; the result gains 'losses' -- the reference's dict as Python floats with ALL evaluated windows as one batch
+    (numerators over denominators, so it does not depend on the batch size either) -- and 'loss', their sum.  reference_quirks: how
+    annotation_flags reads a one-hand annotation and how the terms are combined."""
 
     def __init__(self, net, annotations=None, *, joints=None, num_steps: int = 50, dist_max_mm: float = 50, seed: int = 0, batch: int = 256,
-                 n_events: int = 2048, keep_outputs: bool = False):
+                 n_events: int = 2048, keep_outputs: bool = False, losses: bool = False, reference_quirks: bool = True):
         from .events import EventWindowBuilderS
         self.net = net
         self.device = next(net.parameters()).device
@@ -418,6 +454,11 @@ class SyntheticEvaluator:
             self.params = torch.from_numpy(annotation_table(annotations, net.net.n_pose_params)).to(self.device)
         self.num_steps, self.dist_max_mm, self.seed, self.batch = int(num_steps), float(dist_max_mm), int(seed), int(batch)
         self.keep_outputs = bool(keep_outputs)
+        self.losses, self.reference_quirks, self.flags = bool(losses), bool(reference_quirks), None
+        if self.losses:
+            if annotations is None:
+                raise ValueError("losses=True needs `annotations`: the loss compares the predicted parameters with the annotations'")
+            self.flags = torch.from_numpy(annotation_flags(annotations, self.reference_quirks)).to(self.device)
         self.builder = EventWindowBuilderS(self.device, n_events=n_events)
         self.outputs = None
         self._run = None
@@ -446,7 +487,7 @@ class SyntheticEvaluator:
             if tuple(ids.shape) != (W,):
                 raise ValueError("window_ids must hold one number per window")
         f32, f64, i32, i64 = (dict(device=dev, dtype=t) for t in (torch.float32, torch.float64, torch.int32, torch.int64))
-        acc = AccumulatorS(dev, W, self.num_steps)
+        acc = AccumulatorS(dev, W, self.num_steps, loss_state=self.losses)
         C, cap = self.net.net.in_channels, self.builder.cap
         L = _lib.lib()
         run = {
@@ -462,6 +503,13 @@ class SyntheticEvaluator:
             "conf": torch.empty(B, 4, 4, **i32), "ce_num": torch.empty(B, **f64), "ce_den": torch.empty(B, **f64), "ignored": torch.empty(B, **i32),
             "kept": {k: [] for k in ("j3d_left", "j3d_right", "class_logits", "events", "labels", "sample_idx", "fps_init", "pck", "annotation")},
         }
+        if self.losses:
+            coll = CollisionLoss(dev)
+            faces = tuple(device_faces(self.net.hands[s].faces, dev) for s in ("left", "right"))
+            coll._device_faces(faces[0], faces[1], dev)                    # (its one-time conversion, before the loop)
+            run["loss"] = {"collision": coll, "faces": faces, "work": coll.workspace(B, synth.MANO_NV, int(faces[0].shape[0]), dev),
+                           "terms": torch.empty(B, _lib.LOSS_NT, **f64), "flags": torch.empty(B, 3, **i32), "has_gt": torch.empty(B, **i32)}
+            run["kept"].update({k: [] for k in ("params_left", "params_right", "vertices_left", "vertices_right")})
         self._run, self.outputs = run, None
         if W and self.net.net.precision == "auto":
             # the "auto" arithmetic decision compares two forwards on the host: take it now, on the first batch's own inputs, so
@@ -514,6 +562,17 @@ class SyntheticEvaluator:
         joint_metrics_f32_frames(jl, jr, r["gt"], annotation, self.num_steps, self.dist_max_mm, out=(pck, aucb, l1, has_gt))
         segmentation_score(logits, lab, out=(conf, ce_num, ce_den, ignored))
         r["acc"].add(pck, aucb, l1, has_gt, annotation, conf, ce_num, ce_den, ignored, r["ids"][sl], sl.start)
+        if self.losses:
+            lo, K, state = r["loss"], net.n_pose_params, r["acc"].state
+            prm = [_losses._param_rows(out[side], K) for side in ("left", "right")]                 # views of the row matrix: read in place
+            res = _losses.loss_terms(prm[0], prm[1], jl, jr, K, 1, r["gt"], self.flags, self.params, None, annotation,
+                                     out=(lo["terms"][:b], lo["flags"][:b], lo["has_gt"][:b]))
+            penalty = lo["collision"].per_window(out, lo["faces"], work=lo["work"])
+            _losses.loss_accumulate(*res, state["loss_state"], state["loss_scalars"], penalty, r["ids"][sl])
+            if self.keep_outputs:
+                for h, side in enumerate(("left", "right")):
+                    r["kept"][f"params_{side}"].append(prm[h].clone())
+                    r["kept"][f"vertices_{side}"].append(out[side]["vertices"].clone())
         if self.keep_outputs:
             k = r["kept"]
             for name, t in (("j3d_left", jl), ("j3d_right", jr), ("class_logits", logits), ("events", r["events"][:b]), ("labels", lab),
@@ -528,7 +587,12 @@ class SyntheticEvaluator:
         state = r["acc"].host()
         if self.keep_outputs:
             self.outputs = {k: torch.cat(v, 1 if k == "fps_init" else 0) for k, v in r["kept"].items() if v}
-        return finish_metrics_s(state)
+        res = finish_metrics_s(state)
+        if self.losses:
+            res["losses"] = _losses.finish_losses(state["loss_state"], state["ce_num"], state["ce_den"], self.net.net.n_pose_params, 1,
+                                          r["loss"]["collision"].collision_weight, self.reference_quirks)
+            res["loss"] = sum(res["losses"].values())
+        return res
 
     def evaluate(self, table, starts=None, stride: int | None = None, window_ids=None) -> dict:
         """table: ev2hands_amd.events.EventTableS; starts: the windows' first rows (an int, an array, or None for

@@ -587,6 +587,69 @@ int ev2h_eval_s_accumulate(const float* pck, const double* auc, const double* l1
                            double* frame_auc, double* frame_l1, double* frame_ce_num, double* frame_ce_den,
                            int32_t* frame_annotation, int32_t* scalars, ev2h_stream_t stream);
 
+/* ---- the training loss's forward value, term by term (losses.py:105-240: Loss) --------------------------------------------------- */
+/* Slots of a window's `terms` row.  Three terms between the hands, then EV2H_LOSS_PER_HAND terms per hand (left first). */
+#define EV2H_LOSS_INTER_SHAPE 0
+#define EV2H_LOSS_INTER_TRANSL 1
+#define EV2H_LOSS_INTER_J3D 2
+#define EV2H_LOSS_HAND 3
+#define EV2H_LOSS_H_GLOBAL_ORIENT 0
+#define EV2H_LOSS_H_HAND_POSE 1
+#define EV2H_LOSS_H_SHAPE 2
+#define EV2H_LOSS_H_RJ3D 3
+#define EV2H_LOSS_H_J3D 4
+#define EV2H_LOSS_H_TRANSL 5
+#define EV2H_LOSS_H_REG_BETAS 6
+#define EV2H_LOSS_H_REG_POSE 7
+#define EV2H_LOSS_H_J2D 8
+#define EV2H_LOSS_PER_HAND 9
+#define EV2H_LOSS_NT (EV2H_LOSS_HAND + 2 * EV2H_LOSS_PER_HAND)
+#define EV2H_LOSS_NSTATE (EV2H_LOSS_NT + 6)
+/* The masked numerators of every regression term of losses.py: Loss for B windows, one wavefront per window.
+ * Reads, in place:
+ *   params_left / params_right: window b at + b * params_stride floats (0 = dense = 16 + n_pose, else >= that), one row
+ *     global_orient 3 | hand_pose n_pose | betas 10 | transl 3;  j3d_left / j3d_right: window b at + b * j3d_stride floats (0 = 63,
+ *     else >= 63), [21][3] metres -- views of the forward's row matrix work without a copy;
+ *   the targets from tables of A rows, row index[b] (int32; index NULL: row b, which needs A >= B): target_params [A][2][16 + n_pose]
+ *     (the target's hand_pose cut to n_pose, losses.py:190; mode 1 only), target_j3d [A][2][21][3] metres, target_j2d
+ *     [A][2][21][j2d_ld] with j2d_ld >= 2 (mode 0 only; the first two of each joint's j2d_ld values are read), target_flags [A][2][2]
+ *     int32: per hand (valid, handedness).
+ * Writes, per window, and nothing else: terms [B][EV2H_LOSS_NT] float64, flags [B][3] int32 = (interacting, valid_left, valid_right)
+ * with interacting = (handedness_left + handedness_right == 2), has_gt [B] int32.  An index outside [0, A) gives has_gt = 0, zero
+ * terms and flags, and no table is read.
+ * Arithmetic: every elementwise step is a float32 operation rounded as torch's elementwise kernels round it (a - b, a * b, |a|;
+ * F.mse_loss(reduction='none') = (a - b) * (a - b), F.l1_loss = |a - b|); each value is widened to float64, MULTIPLIED by its mask
+ * (losses.py:139 `loss * indices`: not a branch, so a non-finite prediction in a masked window makes the term NaN as upstream) and
+ * summed in float64 in a fixed lane order.
+ * mode 1 (forward_mano_data, :153-206), lower case = prediction:
+ *   INTER_SHAPE  sum (beta_L - beta_R)^2, INTER_TRANSL sum ((t_L - t_R) - (T_L - T_R))^2, INTER_J3D sum ((j_L - j_R) - (J_L - J_R))^2,
+ *   all masked by interacting;  per hand, masked by valid: GLOBAL_ORIENT, HAND_POSE, SHAPE sum (x - X)^2; RJ3D
+ *   sum |(j[1:] - j[0]) * 1000 - (J[1:] - J[0]) * 1000|; J3D sum |j * 1000 - J * 1000|; TRANSL sum |t - T|; REG_BETAS, REG_POSE
+ *   sum (x - x)^2 (0, or NaN for a non-finite x, as upstream's mse_loss(x, x)); J2D 0.
+ * mode 0 (forward_non_mano_data, :208-240):
+ *   INTER_SHAPE as above; INTER_J3D sum |(j_L - j_R) * 1000 - (J_L - J_R) * 1000| (interacting); per hand REG_BETAS sum beta^2 and
+ *   REG_POSE sum pose^2, NOT masked; RJ3D as above (valid); J2D sum over 21 joints x 2 of (proj(j * 1000) - J2d)^2 (valid), proj =
+ *   camera.py: opengl_projection_transform (:10-38) in float32: `projection` (HOST pointer, 16 floats, row-major 4 x 4, read during
+ *   the call and passed to the kernel by value) times (x, y, z, 1) as ((m0 x + m1 y) + m2 z) + m3, / w, (1 - h) * 0.5, then
+ *   * width | height;  the other slots 0.
+ * Returns EV2H_ERR_ARG, before any use, for a null pointer the mode needs, B or A < 1, n_pose outside 1..45, a mode other than 0 / 1,
+ * a stride below its row (overlapping windows), j2d_ld < 2, index == NULL with A < B.  One launch, no host synchronisation. */
+int ev2h_loss_terms(const float* params_left, const float* params_right, size_t params_stride, const float* j3d_left,
+                    const float* j3d_right, size_t j3d_stride, int n_pose, int mode, const float* target_params,
+                    const float* target_j3d, const float* target_j2d, size_t j2d_ld, const int32_t* target_flags, int A,
+                    const int32_t* index, int B, const float* projection, float width, float height, double* terms,
+                    int32_t* flags, int32_t* has_gt, ev2h_stream_t stream);
+/* Folds ev2h_loss_terms' outputs of B windows into a running state.  state [EV2H_LOSS_NSTATE] float64, zeroed before the first call:
+ * [EV2H_LOSS_NT numerators | 3 counts (interacting, valid_left, valid_right) | collision sum, collision count | windows];  scalars
+ * [2] int32, (0, -1) before the first call: windows counted, and stopped_at = the id of the first window with has_gt = 0
+ * (window_ids [B] int32, or NULL: its position in the run), -1 if none.  The windows that count are those in front of the first one
+ * with has_gt = 0, in this call or an earlier one.  collision: optional [B] float64 per-window penalties (CollisionLoss.per_window);
+ * the non-zero ones are summed and counted (losses.py:95-98).  One workgroup, one thread per sum, windows added in order: every
+ * total equals a sequential float64 loop over the windows, whatever the batch size.  EV2H_ERR_ARG for a null terms / flags / has_gt /
+ * state / scalars or B < 1.  One launch, no host synchronisation, capturable. */
+int ev2h_loss_accumulate(const double* terms, const int32_t* flags, const int32_t* has_gt, const double* collision,
+                         const int32_t* window_ids, int B, double* state, int32_t* scalars, ev2h_stream_t stream);
+
 /* ---- two-hand mesh self-collision (next row 8f-4; evaluate_ev2hands_r.py:128-160, utils/__init__.py:106-124) ---------------- */
 /* verts_left / verts_right [B][nv][3] float32 metres (the forward's vertices), faces [nf][3] int32 (nv <= 778, nf <= 1538).
  * The meshes are concatenated as the reference does (left faces, then right faces + nv), vertices scaled by `scale` (1000:
