@@ -106,14 +106,19 @@ __global__ __launch_bounds__(COL_THREADS) void mesh_collision_kernel(ColP p) {
     if constexpr (PHASE != 1)
     for (int f = tid; f < F2; f += COL_THREADS) {
         float lo[3], hi[3];
+        bool nan = false;
 #pragma unroll
         for (int c = 0; c < 3; ++c) {
             const float x0 = sv[3 * sf[3 * f] + c], x1 = sv[3 * sf[3 * f + 1] + c], x2 = sv[3 * sf[3 * f + 2] + c];
             lo[c] = fminf(x0, fminf(x1, x2));
             hi[c] = fmaxf(x0, fmaxf(x1, x2));
+            nan = nan || x0 != x0 || x1 != x1 || x2 != x2;
         }
+        // A triangle with a NaN coordinate is in no pair (the oracle's min / max hand the NaN on and a NaN box meets nothing); fminf /
+        // fmaxf drop the NaN and would box the other vertices, and NaN projections never separate.  The empty box meets no box, not
+        // even another empty one, and leaves the block box below as it is.
 #pragma unroll
-        for (int c = 0; c < 3; ++c) { sbb[6 * f + c] = lo[c]; sbb[6 * f + 3 + c] = hi[c]; }
+        for (int c = 0; c < 3; ++c) { sbb[6 * f + c] = nan ? INFINITY : lo[c]; sbb[6 * f + 3 + c] = nan ? -INFINITY : hi[c]; }
     }
     __syncthreads();
 

@@ -656,7 +656,8 @@ int ev2h_loss_accumulate(const double* terms, const int32_t* flags, const int32_
  * mm) in float32 and tested in float64.  counts [B] = number of unordered triangle pairs that share no vertex index and
  * intersect (separating-axis test, touching counts); pairs [B][max_pairs][2] (optional) = the first max_pairs of them in
  * lexicographic (i < j) order.  The reference obtains its pairs from the un-vendored torch-mesh-isect BVH with a
- * per-triangle candidate cap; this is the uncapped quantity (parity unpinned, oracle/collision_oracle.py). */
+ * per-triangle candidate cap; this is the uncapped quantity (parity unpinned, oracle/collision_oracle.py).
+ * A triangle with a NaN coordinate is in no pair and the other triangles' pairs are unchanged; infinite vertices are undefined. */
 int ev2h_mesh_collisions(const float* verts_left, const float* verts_right, const int32_t* faces_left, const int32_t* faces_right,
                          int B, int nv, int nf, float scale, int max_pairs, int32_t* pairs, int32_t* counts, int max_per_triangle,
                          ev2h_stream_t stream);

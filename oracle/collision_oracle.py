@@ -14,7 +14,10 @@ triangle-triangle test, its de-duplication) cannot be read or run here.  This re
 number of unordered pairs of triangles that (a) share no vertex index and (b) intersect, by the separating-axis test
 (two face normals, nine edge-edge cross products, six in-plane edge normals for parallel planes; touching counts as
 intersecting), all pairs, no cap -- i.e. what the tree approximates.  It is pinned by known-answer cases and by an
-independent edge-pierces-triangle test on random pairs (tests/test_collision.py)."""
+independent edge-pierces-triangle test on random pairs (tests/test_collision.py).
+
+Not-a-number vertices: a triangle with a NaN coordinate is in no pair, and the other triangles' pairs are unchanged (its
+bounding box is NaN -- NumPy's min / max hand NaN on -- and a NaN box meets nothing).  Infinite vertices are undefined."""
 from __future__ import annotations
 
 import numpy as np

@@ -56,6 +56,22 @@ def test_icosphere_pair_counts():
     assert pairs.shape[0] > 0 and (pairs[:, 0] < 320).all() and (pairs[:, 1] >= 320).all()
 
 
+def test_a_triangle_with_a_nan_coordinate_is_in_no_pair():
+    """The oracle's definition for not-a-number vertices: the triangle is in no pair, the other triangles' pairs are unchanged."""
+    v, f = CO.icosphere(2)
+    vl = (v * 0.040).astype(np.float32)
+    vr = (v * 0.040 + np.array([0.05, 0.003, 0.001])).astype(np.float32)
+    clean = CO.collision_pairs(*CO.build_triangles(vl, vr, f, f))
+    face = int(clean[0, 0])                                  # a left face that collides
+    bad = vl.copy()
+    bad[f[face, 2], 0] = np.nan
+    touched = set(np.flatnonzero((f == f[face, 2]).any(1)).tolist())
+    got = CO.collision_pairs(*CO.build_triangles(bad, vr, f, f))
+    keep = np.array([i not in touched and j not in touched for i, j in clean])
+    assert 0 < keep.sum() < clean.shape[0]
+    assert np.array_equal(got, clean[keep])
+
+
 @pytest.mark.gpu
 @pytest.mark.parametrize("level", [2, 3])
 def test_gpu_pairs_match_oracle(level):
