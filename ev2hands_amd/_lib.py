@@ -97,7 +97,7 @@ W_EQUALIZED, W_UNEQUALIZED_OK = 1, 2
 # and for the seeded-draw / recording-evaluation exports (ev2h_event_window_sample_seeded, ev2h_fps_init_seeded, ev2h_joint_metrics_frames,
 # ev2h_eval_accumulate), and for ev2h_events_undistort, and for the synthetic-set evaluation exports (ev2h_event_window_build_s_ranges,
 # ev2h_joint_metrics_f32_frames, ev2h_segmentation_score, ev2h_eval_s_accumulate), and for the loss exports (ev2h_loss_terms,
-# ev2h_loss_accumulate).
+# ev2h_loss_accumulate), and for the augmented training item (ev2h_event_window_build_s_ranges_aug).
 ABI_VERSION = 8     # 8: EV2H_PREC_F16 (one fp16 plane with f16x2's range machinery); 3: F16X2 range records; 4: ev2h_fp_mlp, ev2h_weights.fp1m; 5: window strides of the outputs; 6: ev2h_pack_weights, ev2h_weights.flags; 7: ev2h_sa_desc.xyz_out
 
 PREC = {"f32": 0, "bf16": 1, "f16x2": 2, "bf16x3": 3, "f16": 4}
@@ -130,6 +130,7 @@ EXPORTS = [
     "ev2h_events_undistort",
     "ev2h_event_window_build_s_ranges", "ev2h_joint_metrics_f32_frames", "ev2h_segmentation_score", "ev2h_eval_s_accumulate",
     "ev2h_loss_terms", "ev2h_loss_accumulate",
+    "ev2h_event_window_build_s_ranges_aug",
 ]
 
 _lib = None
@@ -217,6 +218,7 @@ def lib() -> C.CDLL:
     L.ev2h_joint_metrics_frames.argtypes = [vp, vp, vp, ci, vp, ci, ci, C.c_double, vp, vp, vp, vp, vp, vp]
     L.ev2h_eval_accumulate.argtypes = [vp] * 8 + [ci] * 4 + [vp] * 7 + [vp]
     L.ev2h_event_window_build_s_ranges.argtypes = [vp, ci, ci, vp, ci, ci, ci, ci, ci, ci, ci, vp, vp, vp, vp, vp, vp]
+    L.ev2h_event_window_build_s_ranges_aug.argtypes = [vp, ci, ci, vp, ci, ci, ci, ci, ci, ci, ci, vp, vp, ci, C.c_uint64, vp, vp, vp, vp, vp, vp, vp, vp]
     L.ev2h_joint_metrics_f32_frames.argtypes = [vp, vp, C.c_size_t, vp, ci, vp, ci, ci, C.c_double, vp, vp, vp, vp, vp]
     L.ev2h_segmentation_score.argtypes = [vp, C.c_size_t, vp, ci, ci, vp, vp, vp, vp, vp]
     L.ev2h_eval_s_accumulate.argtypes = [vp] * 10 + [ci] * 4 + [vp] * 8 + [vp]

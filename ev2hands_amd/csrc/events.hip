@@ -259,6 +259,126 @@ __global__ __launch_bounds__(EVW_THREADS) void event_window_build_s_ranges_kerne
     if (threadIdx.x == 0) annotation[b] = E ? (int32_t)ev[(size_t)(E - 1) * ev_stride + anno_col] : -1;
 }
 
+// order-preserving map of IEEE doubles to unsigned, and back
+__device__ __forceinline__ unsigned long long time_key_f64(double t) {
+    const unsigned long long u = (unsigned long long)__double_as_longlong(t);
+    return (u >> 63) ? ~u : (u | 0x8000000000000000ull);
+}
+__device__ __forceinline__ double time_of_key_f64(unsigned long long k) {
+    return __longlong_as_double((long long)((k >> 63) ? (k & 0x7fffffffffffffffull) : ~k));
+}
+
+// One seeded noise row (random.hpp, stream 2): j = its number, M = the window's unique pixels (>= 32 wherever a row exists), tin =
+// the window's table in pixel order.  The time is erpc's float32 mean of pixel `src`, widened, plus a rounded u * 1e3.
+struct NoiseRow { float x, y, n_pos, n_neg; };
+__device__ __forceinline__ double seeded_noise_time(unsigned long long seed, uint32_t wid, uint32_t j, uint32_t M, const float* __restrict__ tin) {
+    const ev2h_random::u32x4 a = ev2h_random::window_block(seed, wid, ev2h_random::STREAM_AUGMENT, 1u + 2u * j);
+    const ev2h_random::u32x4 c = ev2h_random::window_block(seed, wid, ev2h_random::STREAM_AUGMENT, 2u + 2u * j);
+    const uint32_t src = ev2h_random::bounded(a.v[2], M - 1u);
+    const double u = ev2h_random::unit_double(c.v[0], c.v[1]);
+    return __dadd_rn((double)tin[(size_t)src * 8 + 2], __dmul_rn(u, 1e3));
+}
+__device__ __forceinline__ NoiseRow seeded_noise_row(unsigned long long seed, uint32_t wid, uint32_t j, int width, int height) {
+    const ev2h_random::u32x4 a = ev2h_random::window_block(seed, wid, ev2h_random::STREAM_AUGMENT, 1u + 2u * j);
+    const uint32_t ps = a.v[3] & 1u;
+    NoiseRow r;
+    r.x = (float)ev2h_random::bounded(a.v[0], (uint32_t)width);
+    r.y = (float)ev2h_random::bounded(a.v[1], (uint32_t)height);
+    r.n_pos = (float)(((a.v[3] >> 8) & 7u) + ps);
+    r.n_neg = (float)(((a.v[3] >> 16) & 7u) + (ps ^ 1u));
+    return r;
+}
+
+// The time sort of an AUGMENTED Ev2Hands-S training item (erpc.py:203-211, augmentations.py:33-73) in place of
+// event_window_timesort_kernel: K noise rows are appended to the window's M unique pixels, the M + K rows are ordered by their
+// float64 times (exact ties in concatenation order: pixels first, then noise rows in their order), the first row's time is
+// subtracted in float64 and the result rounded to float32 once.  The labels are upstream's: the per-EVENT labels followed by K
+// threes, indexed with the sort positions -- sorted row j with source index s gets the raw label of event s if s < E, else 3.
+// The noise is the caller's (noise_rows [B][kmax][5] float64 = (x, y, t_ms, n_pos, n_neg), noise_n [B]; noise_n[b] < 0: the window
+// is not augmented) or drawn here (window_ids; random.hpp stream 2).  A window that is not augmented takes the float32 path of
+// event_window_timesort_kernel, operation for operation.  uniq_count[b] becomes M + K; a window with M + K > cap (or M > cap) gets
+// that count and no table, an empty one (M <= 0) keeps its count.  LDS: lds_n entries of 8 (time key) + 4 (source index) bytes.
+constexpr int EVA_MAX = 8192;
+__global__ __launch_bounds__(EVW_THREADS) void event_window_augment_timesort_kernel(
+    const float* __restrict__ uniq_in, int32_t* __restrict__ uniq_count, int cap, int lds_n, const double* __restrict__ events, int ev_stride, int n_rows,
+    int label_col, const int32_t* __restrict__ starts, int n_events, const double* __restrict__ noise_rows, const int32_t* __restrict__ noise_n, int kmax,
+    unsigned long long seed, const int32_t* __restrict__ window_ids, int width, int height, float* __restrict__ uniq_out, int32_t* __restrict__ labels_out,
+    int32_t* __restrict__ coin_out) {
+    extern __shared__ __attribute__((aligned(16))) char smem_raw[];
+    unsigned long long* tkeys = reinterpret_cast<unsigned long long*>(smem_raw);
+    unsigned* skeys = reinterpret_cast<unsigned*>(tkeys + lds_n);
+    const int b = blockIdx.x, tid = threadIdx.x;
+    const int Mfull = uniq_count[b];
+    const uint32_t wid = window_ids ? (uint32_t)window_ids[b] : 0u;
+    bool aug;
+    if (window_ids) aug = ev2h_random::window_block(seed, wid, ev2h_random::STREAM_AUGMENT, 0u).v[0] >= 0x80000000u;
+    else aug = noise_n[b] >= 0;
+    if (coin_out && tid == 0) coin_out[b] = aug ? 1 : 0;
+    if (Mfull <= 0) return;                                               // empty (0) or more than 32768 events (-1): as the build left it
+    __syncthreads();                                                      // every thread has read the count before thread 0 replaces it
+    const int K = !aug ? 0 : window_ids ? Mfull / 32 : min(noise_n[b], kmax);
+    const int M = aug ? Mfull : min(Mfull, cap);                          // not augmented: today's rule, the first `cap` pixels
+    const int T = M + K;
+    if (aug) {
+        if (tid == 0) uniq_count[b] = T;
+        if (Mfull > cap || T > cap) return;                               // the full count and no table: the samplers refuse the window
+    }
+    const int s0 = starts[b];
+    const int E = (s0 >= 0 && s0 < n_rows) ? min(n_events, n_rows - s0) : 0;      // > 0 here: the window has pixels
+    const double* ev = events + (size_t)s0 * ev_stride;
+    const float* tin = uniq_in + (size_t)b * cap * 8;
+    const double* nz = noise_rows ? noise_rows + (size_t)b * kmax * 5 : nullptr;
+    int n = 1;
+    while (n < T) n <<= 1;                                                // T <= cap <= lds_n, a power of two
+    for (int i = tid; i < n; i += EVW_THREADS) {
+        unsigned long long k = ~0ull;
+        if (i < M) k = time_key_f64((double)tin[(size_t)i * 8 + 2]);
+        else if (i < T) k = time_key_f64(nz ? nz[(size_t)(i - M) * 5 + 2] : seeded_noise_time(seed, wid, (uint32_t)(i - M), (uint32_t)M, tin));
+        tkeys[i] = k;
+        skeys[i] = (unsigned)i;
+    }
+    __syncthreads();
+    for (int k2 = 2; k2 <= n; k2 <<= 1) {
+        for (int j = k2 >> 1; j > 0; j >>= 1) {
+            for (int i = tid; i < n; i += EVW_THREADS) {
+                const int ixj = i ^ j;
+                if (ixj > i) {
+                    const unsigned long long ta = tkeys[i], tc = tkeys[ixj];
+                    const unsigned sa = skeys[i], sc = skeys[ixj];
+                    const bool up = (i & k2) == 0;
+                    const bool gt = ta > tc || (ta == tc && sa > sc);
+                    if (gt == up) { tkeys[i] = tc; tkeys[ixj] = ta; skeys[i] = sc; skeys[ixj] = sa; }
+                }
+            }
+            __syncthreads();
+        }
+    }
+    const double tfirst = time_of_key_f64(tkeys[0]);
+    float* tout = uniq_out + (size_t)b * cap * 8;
+    for (int j = tid; j < T; j += EVW_THREADS) {
+        const int src = (int)skeys[j];
+        float4 r0;
+        float4 r1 = make_float4(0.f, 0.f, 0.f, 0.f);
+        if (src < M) {
+            r0 = *reinterpret_cast<const float4*>(tin + (size_t)src * 8);
+            r1 = *reinterpret_cast<const float4*>(tin + (size_t)src * 8 + 4);
+        } else if (nz) {
+            const double* q = nz + (size_t)(src - M) * 5;
+            r0 = make_float4((float)q[0], (float)q[1], 0.f, (float)q[3]);
+            r1.x = (float)q[4];
+        } else {
+            const NoiseRow q = seeded_noise_row(seed, wid, (uint32_t)(src - M), width, height);
+            r0 = make_float4(q.x, q.y, 0.f, q.n_pos);
+            r1.x = q.n_neg;
+        }
+        // augmented: float64 minus float64, rounded to float32 once (the table is float64 from the concatenation on); otherwise float32
+        r0.z = aug ? (float)__dsub_rn(time_of_key_f64(tkeys[j]), tfirst) : __fsub_rn(r0.z, (float)tfirst);
+        *reinterpret_cast<float4*>(tout + (size_t)j * 8) = r0;
+        *reinterpret_cast<float4*>(tout + (size_t)j * 8 + 4) = r1;
+        labels_out[(size_t)b * cap + j] = (src < E) ? (int32_t)ev[(size_t)src * ev_stride + label_col] : 3;
+    }
+}
+
 __global__ __launch_bounds__(256) void event_window_sample_kernel(const float* __restrict__ uniq, const int32_t* __restrict__ uniq_count, int cap,
                                                                   const int32_t* __restrict__ sample_idx, int N, int width, int height,
                                                                   float* __restrict__ out_cm, const int32_t* __restrict__ uniq_labels,
@@ -418,6 +538,36 @@ extern "C" int ev2h_event_window_build_s_ranges(const double* events, int ev_str
     EV2H_CHECK_LAUNCH();
     // the time sort reads offsets[b] only, i.e. the window's first row: `starts` as they are.  An empty window has count 0 and is skipped there.
     return ev2h_event_window_timesort(uniq_scratch, uniq_count, cap, events, ev_stride, label_col, starts, B, uniq_sorted, labels, stream);
+}
+
+extern "C" int ev2h_event_window_build_s_ranges_aug(const double* events, int ev_stride, int n_rows, const int32_t* starts, int B, int n_events,
+                                                    int width, int height, int cap, int anno_col, int label_col, const double* noise_rows,
+                                                    const int32_t* noise_n, int noise_kmax, uint64_t seed, const int32_t* window_ids,
+                                                    int32_t* uniq_count, float* uniq_scratch, float* uniq_sorted, int32_t* labels,
+                                                    int32_t* annotation, int32_t* coin, ev2h_stream_t stream) {
+    EV2H_CHECK_ARG(width > 0 && height > 0 && (long long)width * height <= EVW_MAX_PIXELS);
+    EV2H_CHECK_ARG(events && starts && uniq_count && uniq_scratch && uniq_sorted && labels && annotation && uniq_scratch != uniq_sorted);
+    EV2H_CHECK_ARG(B > 0 && n_rows > 0 && n_events > 0 && n_events <= EVW_MAX_EVENTS && cap > 0 && cap <= EVA_MAX);
+    EV2H_CHECK_ARG(ev_stride >= 4 && anno_col >= 0 && anno_col < ev_stride && label_col >= 0 && label_col < ev_stride);
+    // exactly one source of noise: the caller's rows, or the seeded draw
+    EV2H_CHECK_ARG((noise_rows != nullptr) == (noise_n != nullptr) && (noise_n != nullptr) != (window_ids != nullptr));
+    EV2H_CHECK_ARG(!noise_rows || noise_kmax > 0);
+    static PerDevice attr_set{};
+    EV2H_ONCE_PER_DEVICE(attr_set,
+        EV2H_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(event_window_build_s_ranges_kernel),
+                                           hipFuncAttributeMaxDynamicSharedMemorySize, EVW_MAX_EVENTS * 4));
+        EV2H_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(event_window_augment_timesort_kernel),
+                                           hipFuncAttributeMaxDynamicSharedMemorySize, EVA_MAX * 12)););
+    event_window_build_s_ranges_kernel<<<B, EVW_THREADS, EVW_MAX_EVENTS * 4, (hipStream_t)stream>>>(events, ev_stride, n_rows, starts, n_events, width, height,
+                                                                                                    cap, anno_col, uniq_count, uniq_scratch, annotation);
+    EV2H_CHECK_LAUNCH();
+    int lds_n = 1;
+    while (lds_n < cap) lds_n <<= 1;
+    event_window_augment_timesort_kernel<<<B, EVW_THREADS, (size_t)lds_n * 12, (hipStream_t)stream>>>(
+        uniq_scratch, uniq_count, cap, lds_n, events, ev_stride, n_rows, label_col, starts, n_events, noise_rows, noise_n, noise_kmax,
+        (unsigned long long)seed, window_ids, width, height, uniq_sorted, labels, coin);
+    EV2H_CHECK_LAUNCH();
+    return EV2H_OK;
 }
 
 extern "C" int ev2h_event_window_sample(const float* uniq, const int32_t* uniq_count, int cap, const int32_t* sample_idx, int B, int N,

@@ -7,6 +7,12 @@
 //   counter = (block, window_id, stream, 0); one block is four 32-bit words
 //   stream 0, the resampling indices: draw n of a window is word n % 4 of block n / 4
 //   stream 1, the four farthest-point-sampling seeds: block 0, words 0..3 = enc.sa1, enc.sa2, left.sa1, right.sa1
+//   stream 2, the training augmentation of an Ev2Hands-S window with M unique pixels (events.hip: event_window_augment_timesort_kernel):
+//     block 0, word 0 is the coin: the window is augmented iff w0 >= 2^31; K = M / 32 noise rows follow
+//     noise row j, block 1 + 2j: x = bounded(w0, width), y = bounded(w1, height), src = bounded(w2, M - 1) (the pixel-order row whose
+//       mean time the noise time starts from), ps = w3 & 1, a = (w3 >> 8) & 7, b = (w3 >> 16) & 7; n_pos = a + ps, n_neg = b + !ps
+//     noise row j, block 2 + 2j: u = ((w0 >> 5) * 2^26 + (w1 >> 6)) * 2^-53, a double in [0, 1) with 53 random bits;
+//       t = (double)t_avg[src] + u * 1e3, the product rounded before the sum
 //   a 32-bit word u becomes an index below M by multiply-shift, (u * M) >> 32 in 64 bits.  There is NO rejection step, so the
 //   indices are not exactly uniform: some values are hit by ceil(2^32 / M) words and the others by floor(2^32 / M), a relative
 //   bias of at most M / 2^32 -- below 7.7e-6 for M <= 32768 (the largest table a window can have).
@@ -19,7 +25,7 @@ namespace ev2h_random {
 
 constexpr uint32_t PHILOX_M0 = 0xD2511F53u, PHILOX_M1 = 0xCD9E8D57u;        // round multipliers
 constexpr uint32_t PHILOX_W0 = 0x9E3779B9u, PHILOX_W1 = 0xBB67AE85u;        // key increments (Weyl sequence)
-constexpr uint32_t STREAM_SAMPLE = 0, STREAM_FPS = 1;
+constexpr uint32_t STREAM_SAMPLE = 0, STREAM_FPS = 1, STREAM_AUGMENT = 2;
 
 struct u32x4 { uint32_t v[4]; };
 
@@ -44,6 +50,11 @@ __device__ __forceinline__ u32x4 window_block(uint64_t seed, uint32_t window_id,
 
 // u -> [0, bound): the high word of the 64-bit product
 __device__ __forceinline__ uint32_t bounded(uint32_t u, uint32_t bound) { return (uint32_t)(((uint64_t)u * (uint64_t)bound) >> 32); }
+
+// two words -> a double in [0, 1) with 53 random bits (exact: the integer fits a double's significand)
+__device__ __forceinline__ double unit_double(uint32_t w0, uint32_t w1) {
+    return (double)(((uint64_t)(w0 >> 5) << 26) | (uint64_t)(w1 >> 6)) * 0x1p-53;
+}
 
 // resampling index n of a window with M unique pixels
 __device__ __forceinline__ int sample_index(uint64_t seed, uint32_t window_id, uint32_t n, uint32_t M) {

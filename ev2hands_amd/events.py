@@ -169,8 +169,10 @@ class EventTableS:
 
 
 class EventWindowBuilderS(EventWindowBuilder):
-    """The synthetic-dataset (Ev2Hands-S) item builder, /root/reference/src/Ev2Hands/dataset/erpc.py:169-249 with augment off:
-    windows are [n, 6] float64 tables (x, y, t_ns, p, annotation_index, event_label).  Timestamps are accumulated as they are,
+    """The synthetic-dataset (Ev2Hands-S) item builder, /root/reference/src/Ev2Hands/dataset/erpc.py:169-249.  `__call__` builds the
+    item with augment off; `accumulate_ranges(..., noise=...)` / `(..., augment=...)` builds the augmented training item (:203-204,
+    dataset/augmentations.py:33-73) for windows of a resident table, and ev2hands_amd.train_data.TrainingBatcherS the collated batch.
+    Windows are [n, 6] float64 tables (x, y, t_ns, p, annotation_index, event_label).  Timestamps are accumulated as they are,
     the per-pixel means are scaled by 1e-6, the unique pixels are ordered by mean time (first one's time subtracted) and the
     labels are gathered the way erpc.py:209 does.  `sampling=False` keeps all M pixels and pads with N - M resampled ones
     (:220-227).  Returns {'events': [B,5,N] float32, 'class_logits': [B,N] int64} like the dataset item."""
@@ -179,7 +181,7 @@ class EventWindowBuilderS(EventWindowBuilder):
         super().__init__(device, n_events, width, height, cap)
         self.raw_time = 1
 
-    def accumulate_ranges(self, table, starts, out=None, scratch=None):
+    def accumulate_ranges(self, table, starts, out=None, scratch=None, *, noise=None, augment=None, coin=None):
         """The sorted tables of `__call__` for windows cut on the device: window b = rows starts[b] .. min(starts[b] + n_events, E) - 1
         of a resident EventTableS (starts: contiguous device int32 [B]; a start outside [0, E) gives an empty window, count 0 --
         EventTableS.starts checks on the host).  Nothing is uploaded and nothing read back.
@@ -187,7 +189,18 @@ class EventWindowBuilderS(EventWindowBuilder):
         bit for bit those of `__call__` on the same windows cut on the host (self.table / self.table_labels), annotation = column 4
         of each window's last row (erpc.py:200).  Draw with `sample_seeded(sorted_table, counts, seed, ids, labels=labels)`.
         `out`: such a 4-tuple to write into (labels beyond a window's count are left as they are); `scratch`: float32 [B, cap, 8]
-        for the unsorted table."""
+        for the unsorted table.
+
+        The AUGMENTED training item (erpc.py:203-211 with augment on; ev2h_event_window_build_s_ranges_aug, cap <= 8192) with one of
+          noise=(rows, n)            rows float64 [B, Kmax, 5] = (x, y, t_ms, n_pos, n_neg), n int32 [B] (arrays or device tensors): the
+                                     first n[b] rows are appended to window b as they are -- the reference-order path, like
+                                     `sample(..., sample_idx)`; n[b] = -1: window b is not augmented (today's float32 path).
+          augment=(seed, window_ids) the coin and the noise are drawn on the device (csrc/random.hpp, stream 2): window k's item depends
+                                     on (seed, k) alone.  The project's own draws, not numpy's.  window_ids: contiguous device int32 [B].
+        counts[b] becomes M + K, the table's M + K rows are in float64 time order (ties: pixels before noise rows), a noise row's label
+        is 3 unless its source index is below the window's number of events (upstream's quirk).  A window with M + K > cap gets its
+        count and no table: `sample_seeded` refuses it through `status`.  `coin`: device int32 [B] that receives 1 where a window was
+        augmented.  With neither argument this is the plain call, unchanged."""
         if not isinstance(table, EventTableS):
             raise TypeError("EventWindowBuilderS.accumulate_ranges takes an EventTableS")
         B = int(starts.shape[0])
@@ -205,6 +218,39 @@ class EventWindowBuilderS(EventWindowBuilder):
                                    (annotation, (B,), torch.int32, "annotation")):
             if tuple(t.shape) != shape or t.dtype != dt or t.device != dev or not t.is_contiguous():
                 raise ValueError(f"{name} must be a contiguous {dt} tensor {list(shape)} on {dev}")
+        if noise is not None or augment is not None:
+            if noise is not None and augment is not None:
+                raise ValueError("give `noise` or `augment`, not both")
+            if self.cap > 8192:
+                raise ValueError("the augmented time sort holds at most 8192 rows per window: cap <= 8192")
+            rows = n = ids = None
+            seed, kmax = 0, 0
+            if noise is not None:
+                rows, n = noise
+                rows = (rows if torch.is_tensor(rows) else torch.from_numpy(np.ascontiguousarray(rows, dtype=np.float64))).to(dev)
+                n = (n if torch.is_tensor(n) else torch.from_numpy(np.ascontiguousarray(n, dtype=np.int32))).to(dev)
+                if rows.dim() != 3 or rows.shape[0] != B or rows.shape[2] != 5 or rows.shape[1] < 1 or rows.dtype != torch.float64 or not rows.is_contiguous():
+                    raise ValueError(f"noise rows must be a contiguous float64 [{B}, Kmax >= 1, 5] tensor")
+                if tuple(n.shape) != (B,) or n.dtype != torch.int32 or not n.is_contiguous():
+                    raise ValueError(f"noise counts must be a contiguous int32 [{B}] tensor")
+                kmax = int(rows.shape[1])
+            else:
+                seed, ids = augment
+                if not 0 <= int(seed) < 2 ** 64:
+                    raise ValueError("seed must be an unsigned 64-bit integer")
+                if not torch.is_tensor(ids) or ids.dtype != torch.int32 or ids.device != dev or not ids.is_contiguous() or tuple(ids.shape) != (B,):
+                    raise ValueError("window_ids must be a contiguous int32 device tensor [B]")
+            if coin is not None and (tuple(coin.shape) != (B,) or coin.dtype != torch.int32 or coin.device != dev or not coin.is_contiguous()):
+                raise ValueError(f"coin must be a contiguous int32 [{B}] tensor on {dev}")
+            if B:
+                _lib.check(_lib.lib().ev2h_event_window_build_s_ranges_aug(table.events.data_ptr(), table.stride, table.n_rows, starts.data_ptr(), B, self.n,
+                                                                           self.w, self.h, self.cap, EventTableS.ANNOTATION_COL, EventTableS.LABEL_COL,
+                                                                           _lib.ptr(rows), _lib.ptr(n), kmax, int(seed), _lib.ptr(ids), counts.data_ptr(),
+                                                                           scratch.data_ptr(), sorted_t.data_ptr(), labels.data_ptr(), annotation.data_ptr(),
+                                                                           _lib.ptr(coin), _lib.stream_handle()), "ev2h_event_window_build_s_ranges_aug")
+            return sorted_t, counts, labels, annotation
+        if coin is not None:
+            raise ValueError("`coin` goes with `noise` or `augment`")
         if B:
             _lib.check(_lib.lib().ev2h_event_window_build_s_ranges(table.events.data_ptr(), table.stride, table.n_rows, starts.data_ptr(), B, self.n,
                                                                    self.w, self.h, self.cap, EventTableS.ANNOTATION_COL, EventTableS.LABEL_COL,

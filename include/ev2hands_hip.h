@@ -421,6 +421,26 @@ int ev2h_event_window_build_s_ranges(const double* events, int ev_stride, int n_
                                      int width, int height, int cap, int anno_col, int label_col, int32_t* uniq_count,
                                      float* uniq_scratch, float* uniq_sorted, int32_t* labels, int32_t* annotation,
                                      ev2h_stream_t stream);
+/* The AUGMENTED training item of the same windows (erpc.py:203-211 with augment on, augmentations.py:33-73):
+ * ev2h_event_window_build_s_ranges' build step, then a time sort that appends K noise rows to a window's M unique pixels, orders
+ * the M + K rows by their float64 times (exact ties in concatenation order: pixels, then noise rows), subtracts the first row's
+ * time in float64 and rounds to float32 once.  labels: sorted row j with source index s gets the raw label of the window's event
+ * s if s < E (its number of rows), else 3 -- upstream indexes (event labels ++ K threes) with the sort positions.  uniq_count[b]
+ * = M + K.  Exactly one source of noise:
+ *   explicit   noise_rows [B][noise_kmax][5] float64 (x, y, t_ms, n_pos, n_neg) and noise_n [B]: the first noise_n[b] rows are
+ *              appended as they are (more than noise_kmax: the first noise_kmax); noise_n[b] < 0: window b is NOT augmented and
+ *              takes ev2h_event_window_timesort's float32 path bit for bit.  window_ids = NULL, seed ignored.
+ *   seeded     window_ids [B] (noise_rows = noise_n = NULL): Philox4x32-10 under counter (block, window id, 2, 0), csrc/random.hpp:
+ *              block 0 word 0 >= 2^31 augments the window, K = M / 32, noise row j from blocks 1 + 2j and 2 + 2j.  A function of
+ *              (seed, window id) and the window's rows alone.
+ * coin [B] (optional): 1 where the window was augmented.  A window with M + K > cap, or M > cap, gets its full count and no table
+ * (ev2h_event_window_sample_seeded refuses it); an empty window keeps count 0; a window that is not augmented keeps today's rule
+ * (count M, the first min(M, cap) pixels sorted).  cap <= 8192.  Two launches, no host synchronisation, capturable. */
+int ev2h_event_window_build_s_ranges_aug(const double* events, int ev_stride, int n_rows, const int32_t* starts, int B, int n_events,
+                                         int width, int height, int cap, int anno_col, int label_col, const double* noise_rows,
+                                         const int32_t* noise_n, int noise_kmax, uint64_t seed, const int32_t* window_ids,
+                                         int32_t* uniq_count, float* uniq_scratch, float* uniq_sorted, int32_t* labels,
+                                         int32_t* annotation, int32_t* coin, ev2h_stream_t stream);
 /* Resampling + pc_normalize: sample_idx [B][N] int32 (the reference draws them with np.random.choice on the host; for erpc.py's
  * sampling=False branch pass arange(M) followed by the N - M drawn indices) -> out_cm [B][5][N] float32 = (x, y, t, pos_cnt,
  * neg_cnt), the hot path's input.  uniq_labels [B][cap] / out_labels [B][N] int64 optional (Ev2Hands-S 'class_logits' target). */
