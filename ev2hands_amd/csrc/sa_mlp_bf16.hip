@@ -49,6 +49,7 @@ struct SaBP {
     const int32_t* cnt; int cnt_ld;       // optional distinct-neighbour counts (ev2h_sa_desc.cnt)
     float u2, u3;                         // power-of-two unscale factors of the W2s / W3s planes (ev2h_sa_desc.w2_unscale)
     int per_xcd;                          // resident variant: groups per XCD (multiple of 8); nblk is a multiple of 8
+    int pers;                             // streamed set abstraction: 1 = persistent grid (a multiple of 8 workgroups), XCD ranges of per_xcd groups
     // f16x2 activation range (ev2h_sa_desc; NULL p1_scale = off)
     const float* p1_scale; const unsigned* p1_amax;   // per window: power of two the P1 table was stored with, max |stored P1|
     float w1x_norm, dmax, w2_norm, b2_max;
@@ -143,6 +144,8 @@ struct SaBCfg {
     // resident variant: every tile image of the module stays in LDS for the lifetime of the (persistent) workgroup
     static constexpr int RES_W = (NC1 * TB2 + T3 * TB3 + 1023) / 1024 * 1024;
     static constexpr int RES_LDS_BYTES = RES_W + SMALL;
+    // streamed set abstraction: b3 and b1 behind everything else (fits() keeps 2 KiB of the 160 KiB free)
+    static constexpr int SAB_XTR = (C3 + C1) * 4;
     static constexpr bool FITS_RESIDENT = RES_LDS_BYTES <= 160 * 1024 && C1 >= 64;   // (the 32-32-64 MLP is faster streamed: several small workgroups per CU)
     // F16X2 with 1..4 channels left over after the last full 32-channel tile (C2 = 196: channels 192..195): the three plane
     // products of those channels share MFMAs instead of taking three each (csrc/pack.hip builds the matching images):
@@ -155,7 +158,25 @@ struct SaBCfg {
     static constexpr bool PACK4 = (NS == 2) && REM >= 1 && REM <= 4;
 };
 
-// RES = false: weight tiles are streamed, two LDS buffers, one barrier per tile (any MLP width).
+// RES = false: weight tiles are streamed, two LDS buffers, one barrier per tile (any MLP width).  A workgroup works on an OCTET: 8
+//              consecutive groups, one per wave.  Set abstraction (MODE 0 / 3), persistent form (SaBP::pers, chosen by launch_sab when
+//              the launch has more octets than one resident wave of workgroups -- the wide MLPs at 92-152 KB of LDS run one
+//              workgroup per CU, so the headline step's 4096 octets were 16 workgroups one after the other on every CU, each paying
+//              its dispatch, the layer-1 images, the first W2 tile, its head loads and the first index -> row gather with nothing
+//              else on the CU to hide them): 256 x workgroups-per-CU workgroups; XCD x owns the groups [x per_xcd, (x + 1) per_xcd)
+//              as in the resident variant and its workgroups sweep them together, octet slot, slot + nbx, ... -- the same order in
+//              which the dispatcher handed the parent's workgroups to that XCD, so the P1 tables and index lists have the same L2
+//              locality.  Per workgroup, once: layer-1 images, sb2, b3 / b1 in LDS, the first W2 tile.  Carried from octet to octet:
+//                * the weight ring -- the last layer-3 step of an octet fetches W2's first tile for the next octet as it does for
+//                  the next strip (buf keeps its parity: any number of tile steps per octet);
+//                * the head -- centroid, cnt, the window's range record and scale (wave-uniform) are requested an octet ahead, the
+//                  first strip's indices and rows during the last live strip (XPF across the octet boundary; not BF16X3, as XPF);
+//                * the workgroup's strip count -- every wave publishes its NEXT octet's count before the current octet's last
+//                  barrier (s_strips): no barrier of its own, where the one-octet form had two.
+//              Every wave takes the same number of octets (barriers inside); a wave whose group is past the end computes a clamped
+//              group and stores nothing.  Each group's arithmetic is what it was: results are bit-identical to the one-octet form,
+//              which small launches and the spread path (spg > 1) still take -- as one iteration of the same loop.
+//              Measured (profiles/sa_streamed_fixed_cost.txt, profiles/sa_persistent_ab.txt).
 // RES = true : all tile images of the module fit in LDS (the three narrow MLPs of sa1): they are loaded once by a
 //              persistent workgroup whose waves then walk their groups with NO barrier and no DMA in the loop -- the
 //              waves drift apart, so one wave's split (VALU) phases run under the other waves' MFMA phases, and a tile
@@ -308,6 +329,13 @@ __global__ __launch_bounds__(SAB_THREADS, (sab_min_waves<C1, C2, C3, NS, RES, MO
     auto dma_w2 = [&](int step, char* dst) { dma_tile(p.W2s + (size_t)step * CPT * Cfg::TB2, dst, CPT * Cfg::TB2); };
     auto dma_w3 = [&](int step, char* dst) { dma_tile(p.W3s + (size_t)step * UPT * Cfg::TB3, dst, UPT * Cfg::TB3); };
 
+    // persistent streamed variant (SaBP::pers, set abstraction only): see the comment above the kernel
+    constexpr bool PERS = !RES && !ROWS;
+    const bool pers = PERS && p.pers;
+    if constexpr (PERS) {
+        // a workgroup without an octet (the last XCD's range may be shorter than the others'): nothing to do, before any DMA or barrier
+        if (pers && (int)(blockIdx.x & 7) * p.per_xcd + (int)(blockIdx.x >> 3) * WV >= min(p.B * p.S, ((int)(blockIdx.x & 7) + 1) * p.per_xcd)) return;
+    }
     int buf = 0;
     if constexpr (RES && F16) {
         if (tid < Cfg::REC_SLOTS) reinterpret_cast<unsigned*>(smem + WBYTES + Cfg::SMALL_NOREC)[tid] = 0u;      // per-window running maxima of the record combine
@@ -318,31 +346,108 @@ __global__ __launch_bounds__(SAB_THREADS, (sab_min_waves<C1, C2, C3, NS, RES, MO
     } else {
         dma_w2(0, wt0);
     }
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __syncthreads();
-
     // RES: XCD x (= blockIdx & 7, the dispatcher's round-robin) owns the contiguous groups [x * per_xcd, (x + 1) * per_xcd);
     // its nblk/8 workgroups sweep that range together, 8 groups per workgroup per step, so that at any time one XCD works on
     // a few neighbouring windows whose P1 tables and index lists stay in its L2 (a workgroup-contiguous split measured 4.5x
-    // the algorithmic HBM traffic: 32 windows in flight per XCD do not fit the 4 MB L2)
-    const int xcd = blockIdx.x & 7, slot = blockIdx.x >> 3, nbx = p.nblk >> 3;
-    const int g_end = RES ? min(ngroups, (xcd + 1) * p.per_xcd) : ngroups;
-  const int spg = (RES || ROWS) ? 1 : max(1, __builtin_amdgcn_readfirstlane(p.spg)), sw = wave % spg;      // sw: this wave's strip of its group
-  for (int g = (RES ? xcd * p.per_xcd + slot * WV : (spg > 1 ? L * (WV / spg) + wave / spg : L * WV)) + wave * (RES || spg == 1); RES ? g < g_end : true;
-       g += nbx * WV) {
-    const bool valid = g < ngroups;
+    // the algorithmic HBM traffic: 32 windows in flight per XCD do not fit the 4 MB L2).  The persistent streamed variant (pers)
+    // walks the same ranges an octet -- 8 consecutive groups, one per wave -- at a time.
+    const int xcd = blockIdx.x & 7, slot = blockIdx.x >> 3, nbx = RES ? p.nblk >> 3 : (int)(gridDim.x >> 3);
+    const int g_end = (RES || pers) ? min(ngroups, (xcd + 1) * p.per_xcd) : ngroups;
+    const int spg = (RES || ROWS) ? 1 : max(1, __builtin_amdgcn_readfirstlane(p.spg)), sw = wave % spg;      // sw: this wave's strip of its group
+    int g = ((RES || pers) ? xcd * p.per_xcd + slot * WV : (spg > 1 ? L * (WV / spg) + wave / spg : L * WV)) + wave * (RES || spg == 1);
+    constexpr bool fform = fmode || (L1M && hasfeat);           // layer 1 reads raw feature rows (no table, no producer that chose s1)
+    // PERS: what a group needs before its first strip -- centroid, live strips, the window's range record and scale -- is loaded one
+    // octet AHEAD (wave-uniform values), and so is its first strip's gather (below, XPF)
+    // PERS: the octet loop would keep every kernel argument that its head or its epilogue reads in a scalar register THROUGH the strip
+    // loops (about 40: the compiler loads an argument once, at the kernel's entry), where the parent's single pass had them dead or not
+    // yet loaded -- and the widest instantiations have no register to give.  Head and epilogue therefore read their arguments through
+    // a pointer to the kernel-argument segment that is made opaque once per octet (HA): they are loaded again where they are
+    // needed, from the scalar cache.  (SaBP is the kernel's only argument: offset 0 of the segment.)
+    typedef const SaBP __attribute__((address_space(4)))* KargP;
+    KargP pk = (KargP)__builtin_amdgcn_kernarg_segment_ptr();
+#define HA(f) (PERS ? pk->f : p.f)
+    struct Head { bool valid; int b; size_t gf; };
+    auto head_of = [&](int g_) {
+        Head h;
+        h.valid = g_ < ngroups;
+        const int gg_ = h.valid ? g_ : ngroups - 1;
+        h.b = gg_ / HA(S);
+        h.gf = ROWS ? (size_t)gg_ : (size_t)h.b * HA(S_total) + HA(s_off) + (gg_ - h.b * HA(S));
+        return h;
+    };
+    // Slots >= cnt of a group repeat slot 0 (ball-query padding, pointnet2_utils.py:104-106): 32-slot strips made only of
+    // padding cannot change the max and are skipped.  In the streamed variant every wave still walks the tile steps of the
+    // workgroup's longest group (DMA pieces and barriers), without computing.
+    auto strips_of = [&](Head h) {
+        int n = ROWS ? 1 : HA(K) >> 5;
+        if (!ROWS && HA(cnt)) n = min(n, max(1, (HA(cnt)[h.gf * HA(cnt_ld)] + 31) >> 5));
+        if (spg > 1) n = (h.valid && sw < n) ? 1 : 0;      // spread: this wave owns strip sw of its group (or nothing)
+        return n;
+    };
+    float4 ctr_n = make_float4(0.f, 0.f, 0.f, 0.f);
+    int strips_n = 0;
+    unsigned amax_n = 0u;
+    float scale_n = 1.f;
+    auto load_head = [&](Head h) {
+        ctr_n = HA(ctr4)[h.gf];
+        strips_n = strips_of(h);
+        if constexpr (F16) {
+            if (fform && HA(feat_amax)) amax_n = HA(feat_amax)[h.b];
+            else if (!fform && HA(p1_amax)) { amax_n = HA(p1_amax)[h.b]; scale_n = HA(p1_scale)[h.b]; }
+        }
+    };
+    // PERS: the workgroup's strip count of an octet = the largest of its waves'.  Each wave publishes its count of the NEXT octet
+    // (one byte, two alternating sets of 8) before the last barrier of the current one, so the exchange costs no barrier of its own;
+    // a wave that is already an octet ahead writes the other set, never the one a lagging wave still reads.
+    unsigned char* s_strips = reinterpret_cast<unsigned char*>(smem + WBYTES + Cfg::W1B + T2 * 32 * 4);
+    int par = 0;
+    // PERS: b3, and the b1 the F16 feature-row form scales per window, stay in LDS behind the streamed variant's other regions (SAB_XTR):
+    // an octet's head and epilogue then wait for LDS, not for global memory
+    float* sb3 = reinterpret_cast<float*>(smem + Cfg::LDS_BYTES);
+    float* sb1u = sb3 + C3;
+    const Head h0 = head_of(g);
+    bool hc_valid = h0.valid; int hc_b = h0.b; size_t hc_gf = h0.gf;              // PERS: this wave's group of the current octet (one division per octet: the next one's, below)
+    if constexpr (PERS) {
+        for (int i = tid; i < C3; i += WV * 64) sb3[i] = p.b3[i];
+        if constexpr (L1F && F16) {
+            if (fmode) for (int i = tid; i < C1; i += WV * 64) sb1u[i] = p.b1[i];
+        }
+        load_head(h0);
+        if (lane == 0) s_strips[wave] = (unsigned char)strips_n;
+    }
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    __syncthreads();
+
+    // XPF state (see below): carried from strip to strip and, PERS, from octet to octet
+    f32x4 raw[4];                 // a lane's 16 gathered layer-1 values of the current chunk (XPF: survives into the next strip)
+    int idx_cur = 0, idx_nxt = 0;
+    float4 q_cur = make_float4(0.f, 0.f, 0.f, 0.f), f0_cur = q_cur, f1_cur = q_cur;
+    bool pref = false;            // this octet's first gather was requested during the previous octet
+    float s1_prev = __uint_as_float(0x7fc00000u);       // the s1 this wave's sbw / sb1w hold (NaN: none yet)
+  for (; RES ? g < g_end : true; g += nbx * WV) {
+    if constexpr (PERS) asm volatile("" : "+s"(pk));
+    const bool valid = PERS ? hc_valid : g < ngroups;
     const int gg = valid ? g : ngroups - 1;
-    const int b = gg / p.S;
+    const int b = PERS ? hc_b : gg / HA(S);
     // index of this group in the caller's arrays (centroids, index lists, counts, output rows)
-    const size_t gf = ROWS ? (size_t)gg : (size_t)b * p.S_total + p.s_off + (gg - b * p.S);
+    const size_t gf = PERS ? hc_gf : ROWS ? (size_t)gg : (size_t)b * HA(S_total) + HA(s_off) + (gg - b * HA(S));
     float mrun[T3];
 #pragma unroll
     for (int u = 0; u < T3; ++u) mrun[u] = -INFINITY;
 
     float4 ctr = make_float4(0.f, 0.f, 0.f, 0.f);
     const int32_t* gi = nullptr;
-    if constexpr (!ROWS) { ctr = p.ctr4[gf]; gi = p.gidx + gf * p.K + sw * 32; }
-    const int row0 = ROWS ? (gg - b * p.S) * 32 : 0;          // ROWS: first point of this strip inside its window
+    if constexpr (!ROWS) { if constexpr (PERS) ctr = ctr_n; else ctr = HA(ctr4)[gf]; gi = HA(gidx) + gf * HA(K) + sw * 32; }
+    // PERS: this octet's head has arrived; the next octet's (same slot of the XCD range, nbx octets on) is requested now
+    const int my_strips_pers = strips_n;
+    const unsigned hamax = amax_n;
+    const float hscale = scale_n;
+    const bool more_oct = pers && (g - wave + nbx * WV < g_end);          // workgroup-uniform
+    bool hn_valid = valid; int hn_b = b; size_t hn_gf = gf;
+    if constexpr (PERS) {
+        if (more_oct) { const Head h = head_of(g + nbx * WV); load_head(h); hn_valid = h.valid; hn_b = h.b; hn_gf = h.gf; }
+    }
+    const int row0 = ROWS ? (gg - b * HA(S)) * 32 : 0;          // ROWS: first point of this strip inside its window
     unsigned am = 0u;
     // f16x2 range: with P1' = s1 P1 (table stored scaled) and d' = s1 d the layer-1 output is H1' = s1 H1 <= a1 + s1 |W1x|_1 dmax
     // (< 2^15 by the table's choice of s1); layer 2 accumulates (s1 / u2)(W2 H1 + b2); H2' = s2 H2 with the power of two s2 that
@@ -354,37 +459,36 @@ __global__ __launch_bounds__(SAB_THREADS, (sab_min_waves<C1, C2, C3, NS, RES, MO
     // (whole step +6.7 % in a timing build, profiles/r6_f16_chain_scale.txt).  The row chains (ROWS) read rows whose scale
     // their producer chose for the rows alone: they keep the factor.
     constexpr bool C2ONE = NS == 4 && !ROWS;
-    float s1 = 1.f, c2 = p.u2, c3 = C2ONE ? p.u3 * p.u2 : p.u3;      // (without range arguments: s1 = 1; C2ONE: H2' = H2 / u2 as accumulated)
+    float s1 = 1.f, c2 = HA(u2), c3 = C2ONE ? HA(u3) * HA(u2) : HA(u3);      // (without range arguments: s1 = 1; C2ONE: H2' = H2 / u2 as accumulated)
     float so = 1.f;                                             // F16 row chain with fp16 output rows: their per-window power of two
     float b1s_f = 1.f, b1s_x = 1.f, b1s_b = 1.f;               // F16 L1M: the B operand's factors s1 a1f, s1 a1x, s1 a1b (wave-uniform)
-    const bool fform = fmode || (L1M && hasfeat);               // layer 1 reads raw feature rows (no table, no producer that chose s1)
     if constexpr (F16) {
-        if (fform && p.feat_amax) {
+        if (fform && HA(feat_amax)) {
             // no table and no producer that chose s1: the same bound, evaluated here from the record of the feature rows
-            const float bnd = __fmaf_rn(p.w1f_norm, __uint_as_float(p.feat_amax[b]), p.b1_max) + p.w1x_norm * p.dmax;
+            const float bnd = __fmaf_rn(HA(w1f_norm), __uint_as_float(PERS ? hamax : HA(feat_amax)[b]), HA(b1_max)) + HA(w1x_norm) * HA(dmax);
             s1 = f16x2_scale(__float_as_uint(bnd));
-            float s2 = f16x2_scale(__float_as_uint(__fmaf_rn(p.w2_norm, bnd, p.b2_max)));
-            if constexpr (C2ONE) { s1 = fminf(s1, p.u2 * s2); s2 = s1 * pow2_inverse(p.u2); }     // one power of two for the chain: c2 = 1
-            c2 = p.u2 * s2 * pow2_inverse(s1);
-            c3 = p.u3 * pow2_inverse(s2);
-        } else if (!fform && p.p1_amax) {
-            float a1 = __uint_as_float(p.p1_amax[b]);
+            float s2 = f16x2_scale(__float_as_uint(__fmaf_rn(HA(w2_norm), bnd, HA(b2_max))));
+            if constexpr (C2ONE) { s1 = fminf(s1, HA(u2) * s2); s2 = s1 * pow2_inverse(HA(u2)); }     // one power of two for the chain: c2 = 1
+            c2 = HA(u2) * s2 * pow2_inverse(s1);
+            c3 = HA(u3) * pow2_inverse(s2);
+        } else if (!fform && HA(p1_amax)) {
+            float a1 = __uint_as_float(PERS ? hamax : HA(p1_amax)[b]);
             if constexpr (DIRECT) {
-                if (NS == 4 && p.t_bf16) s1 = p.row16_scale[b];                        // fp16 rows: stored with this power of two, the record is of the stored values
-                else { s1 = f16x2_scale(p.p1_amax[b]); a1 *= s1; }                     // unscaled input rows: scaled as they are read
+                if (NS == 4 && HA(t_bf16)) s1 = HA(row16_scale)[b];                        // fp16 rows: stored with this power of two, the record is of the stored values
+                else { s1 = f16x2_scale(HA(p1_amax)[b]); a1 *= s1; }                     // unscaled input rows: scaled as they are read
             }
-            else s1 = p.p1_scale[b];
+            else s1 = PERS ? hscale : HA(p1_scale)[b];
             const float inv_s1 = pow2_inverse(s1);
-            const float bh1 = a1 + s1 * (p.w1x_norm * p.dmax);
-            const float bh2 = __fmaf_rn(p.w2_norm, bh1 * inv_s1, p.b2_max);
+            const float bh1 = a1 + s1 * (HA(w1x_norm) * HA(dmax));
+            const float bh2 = __fmaf_rn(HA(w2_norm), bh1 * inv_s1, HA(b2_max));
             float s2 = f16x2_scale(__float_as_uint(bh2));
-            c2 = p.u2 * s2 * inv_s1;
-            c3 = p.u3 * pow2_inverse(s2);
+            c2 = HA(u2) * s2 * inv_s1;
+            c3 = HA(u3) * pow2_inverse(s2);
             if constexpr (C2ONE) {
                 // the table's producer chose s1 for the whole chain (ev2h_sa_desc.p1_scale, F16 contract): H2' = (s1 / u2) H2 as accumulated.
                 // A scale that breaks the contract would saturate hidden values silently: the window's output is NaN instead.
-                s2 = s1 * pow2_inverse(p.u2);
-                c3 = (s2 * bh2 <= 65504.f) ? p.u3 * pow2_inverse(s2) : __uint_as_float(0x7fc00000u);
+                s2 = s1 * pow2_inverse(HA(u2));
+                c3 = (s2 * bh2 <= 65504.f) ? HA(u3) * pow2_inverse(s2) : __uint_as_float(0x7fc00000u);
             }
         }
         // wave-uniform by construction (one group per wave): keep the three factors in scalar registers
@@ -392,35 +496,34 @@ __global__ __launch_bounds__(SAB_THREADS, (sab_min_waves<C1, C2, C3, NS, RES, MO
         c2 = __uint_as_float(__builtin_amdgcn_readfirstlane(__float_as_uint(c2)));
         c3 = __uint_as_float(__builtin_amdgcn_readfirstlane(__float_as_uint(c3)));
         if constexpr (ROWS && NS == 4) {
-            if (p.out_bf16) {
+            if (HA(out_bf16)) {
                 // fp16 output rows: out' = so out with the power of two so that keeps |W3|_1 bound(H2) + max|b3| below 2^15, bound(H2) =
                 // 2^15 / s2 by the choice of s2 (c3 = u3 / s2).  Folded into the epilogue's factor and bias: out' = acc (c3 so) + b3 so.
-                const float bound2 = 32768.f * (c3 / p.u3);                             // = 2^15 / s2 >= bound(H2)
-                so = f16x2_scale(__float_as_uint(__fmaf_rn(p.w3_norm, bound2, p.b3_max)));
+                const float bound2 = 32768.f * (c3 / HA(u3));                             // = 2^15 / s2 >= bound(H2)
+                so = f16x2_scale(__float_as_uint(__fmaf_rn(HA(w3_norm), bound2, HA(b3_max))));
                 so = __uint_as_float(__builtin_amdgcn_readfirstlane(__float_as_uint(so)));
-                if (lane == 0 && valid && row0 == 0) p.row16_scale[b] = so;            // (one writer per window: its first strip)
+                if (lane == 0 && valid && row0 == 0) HA(row16_scale)[b] = so;            // (one writer per window: its first strip)
             }
         }
-        for (int i = lane; i < T2 * 32; i += 64) sbw[i] = sb2[i] * s1;           // read back by this wave only (LDS ops of a wave stay in order)
-        if constexpr (L1F) {
-            if (fmode) for (int i = lane; i < C1; i += 64) sb1w[i] = p.b1[i] * s1;
+        // (PERS: consecutive octets are mostly of one window -- the wave's copies already hold these values when s1 has not changed)
+        if (!PERS || s1 != s1_prev) {
+            for (int i = lane; i < T2 * 32; i += 64) sbw[i] = sb2[i] * s1;           // read back by this wave only (LDS ops of a wave stay in order)
+            if constexpr (L1F) {
+                if (fmode) for (int i = lane; i < C1; i += 64) sb1w[i] = (PERS ? sb1u[i] : HA(b1)[i]) * s1;
+            }
+            s1_prev = s1;
         }
-        if constexpr (L1M) { b1s_f = s1 * p.a1f; b1s_x = s1 * p.a1x; b1s_b = s1 * p.a1b; }      // (SGPRs: s1 is, the a1 are kernel arguments)
+        if constexpr (L1M) { b1s_f = s1 * HA(a1f); b1s_x = s1 * HA(a1x); b1s_b = s1 * HA(a1b); }      // (SGPRs: s1 is, the a1 are kernel arguments)
     }
-    // Slots >= cnt of a group repeat slot 0 (ball-query padding, pointnet2_utils.py:104-106): 32-slot strips made only of
-    // padding cannot change the max and are skipped.  In the streamed variant every wave still walks the tile steps of the
-    // workgroup's longest group (DMA pieces and barriers), without computing.
-    int my_strips = ROWS ? 1 : p.K >> 5;
-    if (!ROWS && p.cnt) my_strips = min(my_strips, max(1, (p.cnt[gf * p.cnt_ld] + 31) >> 5));
-    if (spg > 1) my_strips = (valid && sw < my_strips) ? 1 : 0;      // spread: this wave owns strip sw of its group (or nothing)
+    const int my_strips = PERS ? my_strips_pers : strips_of(Head{valid, b, gf});
     int nstrips = my_strips;
-    if constexpr (!RES && !ROWS) {
-        int* s_strips = reinterpret_cast<int*>(smem + WBYTES + Cfg::W1B + T2 * 32 * 4);
-        if (tid == 0) *s_strips = 1;
-        __syncthreads();
-        if (lane == 0) atomicMax(s_strips, my_strips);
-        __syncthreads();
-        nstrips = *s_strips;
+    if constexpr (PERS) {
+        // the 8 counts of this octet were published before the barrier that ended the previous one (or the prologue's)
+        const uint2 sv = *reinterpret_cast<const uint2*>(s_strips + par * 8);
+        const unsigned s_lo = __builtin_amdgcn_readfirstlane(sv.x), s_hi = __builtin_amdgcn_readfirstlane(sv.y);
+        nstrips = 1;
+#pragma unroll
+        for (int w = 0; w < 4; ++w) nstrips = max(nstrips, (int)max((s_lo >> (8 * w)) & 0xffu, (s_hi >> (8 * w)) & 0xffu));
     }
 
 #ifdef EV2H_SAB_TIMELINE
@@ -432,11 +535,9 @@ __global__ __launch_bounds__(SAB_THREADS, (sab_min_waves<C1, C2, C3, NS, RES, MO
     // (index -> row: 6 of the 28 us of a strip in the phase timeline, with one workgroup per CU and nothing else to run)
     // (F16X2 and BF16: +0.9 % on the f16x2 step, dominant kernel 1.620 -> 1.576 ms, same-box build A/B profiles/r4_ab_xpf.txt;
     // BF16X3 would spill: its widest instantiation already sits at 256 registers.)
+    // PERS: the first gather of the NEXT octet's group is requested during this group's last strip in the same way (pref).
     constexpr bool XPF = !ROWS && NS != 3;
-    f32x4 raw[4];                 // a lane's 16 gathered layer-1 values of the current chunk (XPF: survives into the next strip)
-    int idx_cur = 0, idx_nxt = 0;
-    float4 q_cur = make_float4(0.f, 0.f, 0.f, 0.f), f0_cur = q_cur, f1_cur = q_cur;
-    if constexpr (XPF) {
+    if (XPF && !pref) {
         idx_cur = gi[l31];
         q_cur = p.pts4[(size_t)b * p.Npts + idx_cur];
         if (hasfeat) {
@@ -449,13 +550,16 @@ __global__ __launch_bounds__(SAB_THREADS, (sab_min_waves<C1, C2, C3, NS, RES, MO
         if constexpr (!RES) {
             if (strip >= my_strips) {           // wave-uniform: keep the workgroup's DMA / barrier sequence, no arithmetic
                 for (int c = 0; c < NC1; ++c) {
-                    char* nxt = buf ? wt0 : wt1;
+                    char* nxt = smem + (buf ^ 1) * Cfg::TILE;
                     if (c % CPT == 0) { if (c + CPT < NC1) dma_w2(c / CPT + 1, nxt); else dma_w3(0, nxt); }
                     if (c % CPT == CPT - 1) { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); __syncthreads(); buf ^= 1; }
                 }
+                if constexpr (PERS) {
+                    if (more_oct && strip + 1 == nstrips && lane == 0) s_strips[(par ^ 1) * 8 + wave] = (unsigned char)strips_n;
+                }
                 for (int u = 0; u < T3; ++u) {
-                    char* nxt = buf ? wt0 : wt1;
-                    if (u % UPT == 0) { if (u + UPT < T3) dma_w3(u / UPT + 1, nxt); else if (strip + 1 < nstrips) dma_w2(0, nxt); }
+                    char* nxt = smem + (buf ^ 1) * Cfg::TILE;
+                    if (u % UPT == 0) { if (u + UPT < T3) dma_w3(u / UPT + 1, nxt); else if (strip + 1 < nstrips || more_oct) dma_w2(0, nxt); }
                     if (u % UPT == UPT - 1) { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); __syncthreads(); buf ^= 1; }
                 }
                 continue;
@@ -521,7 +625,7 @@ __global__ __launch_bounds__(SAB_THREADS, (sab_min_waves<C1, C2, C3, NS, RES, MO
         } else {
             const int idx = XPF ? idx_cur : gi[strip * 32 + l31];
             const float4 q = XPF ? q_cur : p.pts4[(size_t)b * p.Npts + idx];
-            if constexpr (XPF) idx_nxt = (strip + 1 < my_strips) ? gi[(strip + 1) * 32 + l31] : idx_cur;
+            if constexpr (XPF) idx_nxt = (strip + 1 < my_strips) ? gi[(strip + 1) * 32 + l31] : (more_oct ? p.gidx[hn_gf * p.K + l31] : idx_cur);
             dx = __fsub_rn(q.x, ctr.x); dy = __fsub_rn(q.y, ctr.y); dz = __fsub_rn(q.z, ctr.z);
             if constexpr (F16 && !L1M) { if (!fmode) { dx *= s1; dy *= s1; dz *= s1; } }      // exact; with P1' = s1 P1 this makes layer 1 produce s1 H1
             if (fmode) {
@@ -570,7 +674,7 @@ __global__ __launch_bounds__(SAB_THREADS, (sab_min_waves<C1, C2, C3, NS, RES, MO
                     }
                 } else {
                     prow = reinterpret_cast<const float4*>(p.P1 + ((size_t)b * p.Npts + idx) * p.ldp);
-                    if (strip == 0) {          // (later strips: requested during the previous strip's layer 3)
+                    if (strip == 0 && !pref) {          // (later strips: requested during the previous strip's layer 3)
 #pragma unroll
                         for (int j4 = 0; j4 < 4; ++j4) raw[j4] = *reinterpret_cast<const f32x4*>(prow + qi(j4));
                     }
@@ -592,7 +696,7 @@ __global__ __launch_bounds__(SAB_THREADS, (sab_min_waves<C1, C2, C3, NS, RES, MO
                 }
             } else {
                 prow = reinterpret_cast<const float4*>(p.P1 + ((size_t)b * p.Npts + idx) * p.ldp);
-                if (!XPF || strip == 0) {
+                if (!XPF || (strip == 0 && !pref)) {
 #pragma unroll
                     for (int j4 = 0; j4 < 4; ++j4) raw[j4] = *reinterpret_cast<const f32x4*>(prow + qi(j4));
                 }
@@ -771,7 +875,7 @@ __global__ __launch_bounds__(SAB_THREADS, (sab_min_waves<C1, C2, C3, NS, RES, MO
         };
         auto l2_dma = [&](int c) {                      // the next tile step's image into the other buffer
             if constexpr (!RES) {
-                char* nxt = buf ? wt0 : wt1;
+                char* nxt = smem + (buf ^ 1) * Cfg::TILE;
                 if (c % CPT == 0) { if (c + CPT < NC1) dma_w2(c / CPT + 1, nxt); else dma_w3(0, nxt); }
             }
         };
@@ -791,7 +895,7 @@ __global__ __launch_bounds__(SAB_THREADS, (sab_min_waves<C1, C2, C3, NS, RES, MO
 #pragma unroll 1
             for (int c = 0; c < NC1; ++c) {
                 STAMP(2 + 4 * c);
-                char* cur = RES ? smem + c * Cfg::TB2 : (buf ? wt1 : wt0) + (c % CPT) * Cfg::TB2;
+                char* cur = RES ? smem + c * Cfg::TB2 : (smem + buf * Cfg::TILE) + (c % CPT) * Cfg::TB2;
                 l2_dma(c);
 #pragma unroll
                 for (int j4 = 0; j4 < 4; ++j4) finish_slice(c, j4, bpA);
@@ -835,7 +939,7 @@ __global__ __launch_bounds__(SAB_THREADS, (sab_min_waves<C1, C2, C3, NS, RES, MO
             }
             auto l2_step = [&](int c, u32x4 (&bc)[2][NPL], u32x4 (&bn)[2][NPL]) {
                 STAMP(2 + 4 * c);
-                char* cur = RES ? smem + c * Cfg::TB2 : (buf ? wt1 : wt0) + (c % CPT) * Cfg::TB2;
+                char* cur = RES ? smem + c * Cfg::TB2 : (smem + buf * Cfg::TILE) + (c % CPT) * Cfg::TB2;
                 l2_dma(c);
                 const bool more = c + 1 < NC1;
                 if (more) {
@@ -872,15 +976,20 @@ __global__ __launch_bounds__(SAB_THREADS, (sab_min_waves<C1, C2, C3, NS, RES, MO
         }
 
         STAMP(38);
+        if constexpr (PERS) {          // (before the octet's last barrier: see s_strips)
+            if (more_oct && strip + 1 == nstrips && lane == 0) s_strips[(par ^ 1) * 8 + wave] = (unsigned char)strips_n;
+        }
         if constexpr (XPF) {
             // next strip's coordinates and feature row / first table chunk: its index arrived long ago; `raw` is free again
-            if (strip + 1 < my_strips) {
-                q_cur = p.pts4[(size_t)b * p.Npts + idx_nxt];
+            // (PERS, last live strip of the group: the same for the first strip of this wave's group in the next octet, window hn.b)
+            if (strip + 1 < my_strips || more_oct) {
+                const int bx = (strip + 1 < my_strips) ? b : hn_b;
+                q_cur = p.pts4[(size_t)bx * p.Npts + idx_nxt];
                 if (hasfeat) {
-                    const float4* fr = reinterpret_cast<const float4*>(p.feat + ((size_t)b * p.Npts + idx_nxt) * p.ldf);
+                    const float4* fr = reinterpret_cast<const float4*>(p.feat + ((size_t)bx * p.Npts + idx_nxt) * p.ldf);
                     f0_cur = fr[0]; f1_cur = fr[1];
                 } else {
-                    const float4* pn = reinterpret_cast<const float4*>(p.P1 + ((size_t)b * p.Npts + idx_nxt) * p.ldp);
+                    const float4* pn = reinterpret_cast<const float4*>(p.P1 + ((size_t)bx * p.Npts + idx_nxt) * p.ldp);
 #pragma unroll
                     for (int j4 = 0; j4 < 4; ++j4) raw[j4] = *reinterpret_cast<const f32x4*>(pn + qi(j4));
                 }
@@ -952,12 +1061,12 @@ __global__ __launch_bounds__(SAB_THREADS, (sab_min_waves<C1, C2, C3, NS, RES, MO
         auto l3_step = [&](int u, auto first_tag) {
             constexpr bool FIRST = decltype(first_tag)::value;
             STAMP(40 + 4 * u);
-            char* cur = RES ? smem + NC1 * Cfg::TB2 + u * Cfg::TB3 : (buf ? wt1 : wt0) + (u % UPT) * Cfg::TB3;
-            char* nxt = buf ? wt0 : wt1;
+            char* cur = RES ? smem + NC1 * Cfg::TB2 + u * Cfg::TB3 : (smem + buf * Cfg::TILE) + (u % UPT) * Cfg::TB3;
+            char* nxt = smem + (buf ^ 1) * Cfg::TILE;
             if constexpr (!RES) {
                 if (u % UPT == 0) {
                     const bool more_w3 = (u + UPT < T3);
-                    const bool more = more_w3 || (strip + 1 < nstrips);
+                    const bool more = more_w3 || (strip + 1 < nstrips) || more_oct;      // (W2's first tile: of the next strip, or of the next octet)
                     if (more_w3) dma_w3(u / UPT + 1, nxt); else if (more) dma_w2(0, nxt);
                 }
             }
@@ -1070,6 +1179,7 @@ __global__ __launch_bounds__(SAB_THREADS, (sab_min_waves<C1, C2, C3, NS, RES, MO
         for (int u = H2FUSE ? TPS : 0; u < T3; u += TPS) l3_step(u, std::false_type{});
         STAMP(37);
     }
+    if constexpr (PERS) asm volatile("" : "+s"(pk));
     if constexpr (!ROWS && !RES) {
         if (spg > 1) {
             // combine the strips' partial maxima: [wave][C3] floats in the (now idle) tile buffer; the group's first wave finishes
@@ -1095,16 +1205,16 @@ __global__ __launch_bounds__(SAB_THREADS, (sab_min_waves<C1, C2, C3, NS, RES, MO
         for (int u = 0; u < T3; ++u) {
             const float v = fmaxf(mrun[u], __shfl_xor(mrun[u], 32, 64));
             if (valid && half == 0 && sw == 0) {
-                float o = fmaxf(v * c3 + p.b3[32 * u + l31], 0.f);
+                float o = fmaxf(v * c3 + (PERS ? sb3[32 * u + l31] : HA(b3)[32 * u + l31]), 0.f);
                 if constexpr (C2ONE) o = (c3 == c3) ? o : c3;          // (fmaxf drops a NaN: the broken-contract marker must reach the caller)
-                p.out[gf * p.ldo + 32 * u + l31] = o;
+                HA(out)[gf * HA(ldo) + 32 * u + l31] = o;
                 am = max(am, __float_as_uint(o));
             }
         }
     }
     if constexpr (!ROWS) {
-        if (p.xyz_out && valid && sw == 0 && lane < 8)
-            p.xyz_out[gf * p.xyz_ld + lane] = lane == 0 ? ctr.x : lane == 1 ? ctr.y : lane == 2 ? ctr.z : 0.f;
+        if (HA(xyz_out) && valid && sw == 0 && lane < 8)
+            HA(xyz_out)[gf * HA(xyz_ld) + lane] = lane == 0 ? ctr.x : lane == 1 ? ctr.y : lane == 2 ? ctr.z : 0.f;
     }
     if constexpr (F16) {
         // Range record of the output (ev2hands_hip.h "Range records"): amax[b] = max over the window's groups.  One device-scope
@@ -1120,15 +1230,15 @@ __global__ __launch_bounds__(SAB_THREADS, (sab_min_waves<C1, C2, C3, NS, RES, MO
         //    on to the next window -- an under-estimated record, caught by the sharded-equals-unsharded test.)  Windows beyond
         //    the slots (more than 64 windows per XCD) update memory directly.
         // max is exact, associative and idempotent: the record is the same number whatever the route.
-        if (p.out_amax) {
+        if (HA(out_amax)) {
             am = wave_max_u32_dpp(am);
             char* rec = smem + WBYTES + Cfg::SMALL_NOREC;
             if constexpr (RES) {
                 if (lane == 0 && am) {
-                    const int slot = b - (xcd * p.per_xcd) / p.S;          // windows of this XCD's group range, in order
+                    const int slot = b - (xcd * HA(per_xcd)) / HA(S);          // windows of this XCD's group range, in order
                     unsigned old = 0u;
                     if (slot >= 0 && slot < Cfg::REC_SLOTS) old = atomicMax(reinterpret_cast<unsigned*>(rec) + slot, am);
-                    if (am > old) atomicMax(&p.out_amax[b], am);
+                    if (am > old) atomicMax(&HA(out_amax)[b], am);
                 }
             } else {
                 int* sb = reinterpret_cast<int*>(rec);
@@ -1142,12 +1252,18 @@ __global__ __launch_bounds__(SAB_THREADS, (sab_min_waves<C1, C2, C3, NS, RES, MO
                     for (int w = 0; w < WV; ++w) {
                         if (sb[w] == b) { first = first && w >= wave; m = max(m, sa[w]); }
                     }
-                    if (first) atomicMax(&p.out_amax[b], m);
+                    if (first) atomicMax(&HA(out_amax)[b], m);
                 }
             }
         }
     }
-    if constexpr (!RES) break;
+#undef HA
+    if constexpr (!RES) {
+        if (!more_oct) break;
+        par ^= 1;
+        pref = XPF;
+        hc_valid = hn_valid; hc_b = hn_b; hc_gf = hn_gf;
+    }
   }
 }
 
@@ -1177,10 +1293,18 @@ int launch_sab(SaBP p, hipStream_t st) {
             return EV2H_OK;
         }
     }
-    static PerDevice attr_set{};
-    EV2H_ONCE_PER_DEVICE(attr_set,
-        EV2H_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(sa_mlp_max_bf16_kernel<C1, C2, C3, NS, false, MODE>),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, Cfg::LDS_BYTES)););
+    static PerDevice wg_slot_s{};                         // per device: 0 = not set up yet, else streamed workgroups per CU
+    std::atomic<int>& wgs = wg_slot_s.cur();
+    int wg_per_cu = wgs.load(std::memory_order_acquire);
+    if (!wg_per_cu) {
+        auto k = sa_mlp_max_bf16_kernel<C1, C2, C3, NS, false, MODE>;
+        static_assert(Cfg::LDS_BYTES + Cfg::SAB_XTR <= 160 * 1024, "LDS");
+        EV2H_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize, Cfg::LDS_BYTES + Cfg::SAB_XTR));
+        int n = 0;
+        EV2H_CHECK_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, k, SAB_THREADS, Cfg::LDS_BYTES + Cfg::SAB_XTR));
+        wg_per_cu = n > 0 ? n : 1;
+        wgs.store(wg_per_cu, std::memory_order_release);
+    }
     {
         // small grids (a few windows at a time): spread a group's strips over the waves of a workgroup (SaBP::spg).  Chosen by the
         // launch size only -- the result does not depend on it (a max is exact and order-free; test_gpu_schedules.py::test_sa_window_counts at 1 .. 256 windows).
@@ -1191,7 +1315,17 @@ int launch_sab(SaBP p, hipStream_t st) {
             p.nblk = ceil_div(p.B * p.S, SAB_WAVES / spg);
         }
     }
-    sa_mlp_max_bf16_kernel<C1, C2, C3, NS, false, MODE><<<p.nblk, SAB_THREADS, Cfg::LDS_BYTES, st>>>(p);
+    // more group-octets than one resident wave of workgroups: launch that wave and let every workgroup walk the octets of its
+    // XCD's range (the kernel's comment, "persistent streamed variant").  The result does not depend on it -- each group's
+    // arithmetic is the same whichever workgroup computes it (tests/test_gpu_sa_persistent.py).
+    int grid = p.nblk;
+    p.pers = 0;
+    if (p.spg == 1 && p.nblk > 256 * wg_per_cu) {
+        p.pers = 1;
+        p.per_xcd = ceil_div(ceil_div(p.B * p.S, 8), SAB_WAVES) * SAB_WAVES;
+        grid = 256 * wg_per_cu;
+    }
+    sa_mlp_max_bf16_kernel<C1, C2, C3, NS, false, MODE><<<grid, SAB_THREADS, Cfg::LDS_BYTES + Cfg::SAB_XTR, st>>>(p);
     EV2H_CHECK_LAUNCH();
     return EV2H_OK;
 }
