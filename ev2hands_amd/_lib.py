@@ -276,6 +276,17 @@ def ptr(t) -> int:
     return 0 if t is None else t.data_ptr()
 
 
+def _dev_tensor(t, name, dtype, shape, dev=None, contiguous=True):
+    """The tensor contract of the library's callers: `t` is a (contiguous) tensor of `dtype` and `shape` on the CUDA device `dev`
+    (None: any), else ValueError."""
+    import torch
+    if not isinstance(t, torch.Tensor) or t.dtype != dtype or tuple(t.shape) != tuple(shape) or t.device.type != "cuda" \
+            or (dev is not None and t.device != dev) or (contiguous and not t.is_contiguous()):
+        raise ValueError(f"{name} must be a {'contiguous ' if contiguous else ''}{dtype} tensor {list(shape)} on "
+                         f"{dev if dev is not None else 'a CUDA device'}, got {getattr(t, 'dtype', type(t))} {list(getattr(t, 'shape', ()))} "
+                         f"on {getattr(t, 'device', None)}")
+
+
 def stream_handle() -> int:
     import torch
     return torch.cuda.current_stream().cuda_stream

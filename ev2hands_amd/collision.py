@@ -46,9 +46,9 @@ def mesh_collisions(verts_left: torch.Tensor, verts_right: torch.Tensor, faces_l
     nf = fl.shape[0]
     if out is not None:
         counts, pairs = out
-        if counts.dtype != torch.int32 or tuple(counts.shape) != (B,) or counts.device != dev or not counts.is_contiguous() or (max_pairs > 0 and (
-                pairs is None or pairs.dtype != torch.int32 or tuple(pairs.shape) != (B, max_pairs, 2) or pairs.device != dev or not pairs.is_contiguous())):
-            raise ValueError("mesh_collisions: out must be (counts [B] int32, pairs [B, max_pairs, 2] int32), contiguous, on the vertices' device")
+        _lib._dev_tensor(counts, "mesh_collisions: out's counts", torch.int32, (B,), dev)
+        if max_pairs > 0:
+            _lib._dev_tensor(pairs, "mesh_collisions: out's pairs", torch.int32, (B, max_pairs, 2), dev)
     else:
         counts = torch.empty(B, device=dev, dtype=torch.int32)
         pairs = torch.empty(B, max_pairs, 2, device=dev, dtype=torch.int32) if max_pairs > 0 else None

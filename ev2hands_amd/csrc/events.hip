@@ -27,21 +27,53 @@ constexpr int EVW_MAX_EVENTS = 32768;
 // 32766 or 32767 would pack to exactly those two.  So the last pixel a sensor may have is 131070.
 constexpr long long EVW_MAX_PIXELS = (1 << 17) - 1;
 
-// ascending bitonic sort of n (a power of two) 32-bit keys in LDS by the whole workgroup
-__device__ __forceinline__ void bitonic_sort_u32(unsigned* keys, int n, int tid) {
+__host__ __device__ __forceinline__ int pow2_at_least(int v) {
+    int n = 1;
+    while (n < v) n <<= 1;
+    return n;
+}
+
+// The one bitonic network: ascending sort of n (a power of two) LDS positions by the whole workgroup.  load(i) gives the entry at
+// position i (anything with operator>), store(i, e) puts one there.  Both entries of a pair are read whole before they are compared:
+// a "greater" and a "swap" on positions made the compiler read the pair sort's source indices twice, which the clock showed.  Equal
+// entries only ever carry equal payloads here (padding, dropped events, equal frame values, or keys made unique by an index), so
+// the result does not depend on how ties fall.
+template <class Load, class Store>
+__device__ __forceinline__ void bitonic_sort_lds(int n, int tid, Load load, Store store) {
     for (int k2 = 2; k2 <= n; k2 <<= 1) {
         for (int j = k2 >> 1; j > 0; j >>= 1) {
             for (int i = tid; i < n; i += EVW_THREADS) {
                 const int ixj = i ^ j;
                 if (ixj > i) {
-                    const unsigned a = keys[i], c = keys[ixj];
-                    const bool up = (i & k2) == 0;
-                    if ((a > c) == up) { keys[i] = c; keys[ixj] = a; }
+                    const auto a = load(i), c = load(ixj);
+                    if ((a > c) == ((i & k2) == 0)) { store(i, c); store(ixj, a); }
                 }
             }
             __syncthreads();
         }
     }
+}
+template <class Key>
+__device__ __forceinline__ void bitonic_sort_keys(Key* keys, int n, int tid) {
+    bitonic_sort_lds(n, tid, [=](int i) { return keys[i]; }, [=](int i, Key k) { keys[i] = k; });
+}
+
+// order-preserving maps of IEEE floats / doubles to unsigned, and back
+__device__ __forceinline__ unsigned time_key(float t) {
+    const unsigned u = __float_as_uint(t);
+    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
+}
+__device__ __forceinline__ unsigned long long time_key(double t) {
+    const unsigned long long u = (unsigned long long)__double_as_longlong(t);
+    return (u >> 63) ? ~u : (u | 0x8000000000000000ull);
+}
+__device__ __forceinline__ double time_of_key(unsigned long long k) {
+    return __longlong_as_double((long long)((k >> 63) ? (k & 0x7fffffffffffffffull) : ~k));
+}
+
+// rows of the Ev2Hands-S window that starts at row s of an n_rows table (erpc.py:170-174); a start outside the table: none
+__device__ __forceinline__ int window_rows_s(int s, int n_events, int n_rows) {
+    return (s >= 0 && s < n_rows) ? min(n_events, n_rows - s) : 0;
 }
 
 // One window by one workgroup: `ev` = its first row, E = its rows.  STREAM_US = false: column 2 holds the times the reference's
@@ -57,8 +89,7 @@ __device__ __forceinline__ bool event_window_build_body(const double* __restrict
         if (tid == 0) uniq_count[b] = (E <= 0) ? 0 : -1;
         return false;
     }
-    int n = 1;
-    while (n < E) n <<= 1;
+    const int n = pow2_at_least(E);
     for (int i = tid; i < n; i += EVW_THREADS) {
         unsigned k = 0xffffffffu;
         if (i < E) {
@@ -72,7 +103,7 @@ __device__ __forceinline__ bool event_window_build_body(const double* __restrict
         keys[i] = k;
     }
     __syncthreads();
-    bitonic_sort_u32(keys, n, tid);
+    bitonic_sort_keys(keys, n, tid);
     // run heads -> exclusive scan of head flags over contiguous per-thread chunks
     const int chunk = (n + EVW_THREADS - 1) / EVW_THREADS;
     const int lo = tid * chunk, hi = min(lo + chunk, n);
@@ -156,12 +187,11 @@ __global__ __launch_bounds__(EVW_THREADS) void event_window_build_ranges_kernel(
         return;
     }
     __syncthreads();                                                  // the table's last reads of `keys`
-    int n = 1;
-    while (n < E) n <<= 1;
+    const int n = pow2_at_least(E);
     for (int i = tid; i < n; i += EVW_THREADS)                        // signed order -> unsigned order; the padding sorts behind row E-1
         keys[i] = (i < E) ? ((unsigned)(int)ev[(size_t)i * ev_stride + frame_col] ^ 0x80000000u) : 0xffffffffu;
     __syncthreads();
-    bitonic_sort_u32(keys, n, tid);
+    bitonic_sort_keys(keys, n, tid);
     const int chunk = (E + EVW_THREADS - 1) / EVW_THREADS;
     const int lo = tid * chunk, hi = min(lo + chunk, E);
     unsigned long long best = 0;                                      // (run length << 32) | ~key: longest run, smallest value on ties
@@ -202,31 +232,11 @@ __global__ __launch_bounds__(EVW_THREADS) void event_window_timesort_kernel(cons
     const int M = min(uniq_count[b], cap);
     if (M <= 0 || M > EVS_MAX) return;
     const float* tin = uniq_in + (size_t)b * cap * 8;
-    int n = 1;
-    while (n < M) n <<= 1;
-    for (int i = tid; i < n; i += EVW_THREADS) {
-        unsigned long long k = ~0ull;
-        if (i < M) {
-            unsigned u = __float_as_uint(tin[(size_t)i * 8 + 2]);
-            u = (u & 0x80000000u) ? ~u : (u | 0x80000000u);       // order-preserving map of IEEE floats to unsigned
-            k = ((unsigned long long)u << 32) | (unsigned)i;
-        }
-        keys[i] = k;
-    }
+    const int n = pow2_at_least(M);
+    for (int i = tid; i < n; i += EVW_THREADS)
+        keys[i] = (i < M) ? ((unsigned long long)time_key(tin[(size_t)i * 8 + 2]) << 32) | (unsigned)i : ~0ull;
     __syncthreads();
-    for (int k2 = 2; k2 <= n; k2 <<= 1) {
-        for (int j = k2 >> 1; j > 0; j >>= 1) {
-            for (int i = tid; i < n; i += EVW_THREADS) {
-                const int ixj = i ^ j;
-                if (ixj > i) {
-                    const unsigned long long a = keys[i], c = keys[ixj];
-                    const bool up = (i & k2) == 0;
-                    if ((a > c) == up) { keys[i] = c; keys[ixj] = a; }
-                }
-            }
-            __syncthreads();
-        }
-    }
+    bitonic_sort_keys(keys, n, tid);
     const float tfirst = tin[(size_t)(unsigned)(keys[0] & 0xffffffffull) * 8 + 2];
     float* tout = uniq_out + (size_t)b * cap * 8;
     const double* ev = events ? events + (size_t)offsets[b] * ev_stride : nullptr;
@@ -253,19 +263,10 @@ __global__ __launch_bounds__(EVW_THREADS) void event_window_build_s_ranges_kerne
     __shared__ int s_part[EVW_THREADS];
     const int b = blockIdx.x;
     const int s = starts[b];
-    const int E = (s >= 0 && s < n_rows) ? min(n_events, n_rows - s) : 0;
+    const int E = window_rows_s(s, n_events, n_rows);
     const double* ev = events + (size_t)(E ? s : 0) * ev_stride;
     event_window_build_body<false>(ev, E, b, width, height, cap, 1, ev_stride, uniq_count, uniq, reinterpret_cast<unsigned*>(smem_raw), s_part);
     if (threadIdx.x == 0) annotation[b] = E ? (int32_t)ev[(size_t)(E - 1) * ev_stride + anno_col] : -1;
-}
-
-// order-preserving map of IEEE doubles to unsigned, and back
-__device__ __forceinline__ unsigned long long time_key_f64(double t) {
-    const unsigned long long u = (unsigned long long)__double_as_longlong(t);
-    return (u >> 63) ? ~u : (u | 0x8000000000000000ull);
-}
-__device__ __forceinline__ double time_of_key_f64(unsigned long long k) {
-    return __longlong_as_double((long long)((k >> 63) ? (k & 0x7fffffffffffffffull) : ~k));
 }
 
 // One seeded noise row (random.hpp, stream 2): j = its number, M = the window's unique pixels (>= 32 wherever a row exists), tin =
@@ -299,6 +300,11 @@ __device__ __forceinline__ NoiseRow seeded_noise_row(unsigned long long seed, ui
 // event_window_timesort_kernel, operation for operation.  uniq_count[b] becomes M + K; a window with M + K > cap (or M > cap) gets
 // that count and no table, an empty one (M <= 0) keeps its count.  LDS: lds_n entries of 8 (time key) + 4 (source index) bytes.
 constexpr int EVA_MAX = 8192;
+struct TimeSource {                                                       // an entry of its sort: by time key, exact ties by source index
+    unsigned long long t;
+    unsigned s;
+    __device__ bool operator>(const TimeSource& o) const { return t > o.t || (t == o.t && s > o.s); }
+};
 __global__ __launch_bounds__(EVW_THREADS) void event_window_augment_timesort_kernel(
     const float* __restrict__ uniq_in, int32_t* __restrict__ uniq_count, int cap, int lds_n, const double* __restrict__ events, int ev_stride, int n_rows,
     int label_col, const int32_t* __restrict__ starts, int n_events, const double* __restrict__ noise_rows, const int32_t* __restrict__ noise_n, int kmax,
@@ -324,36 +330,21 @@ __global__ __launch_bounds__(EVW_THREADS) void event_window_augment_timesort_ker
         if (Mfull > cap || T > cap) return;                               // the full count and no table: the samplers refuse the window
     }
     const int s0 = starts[b];
-    const int E = (s0 >= 0 && s0 < n_rows) ? min(n_events, n_rows - s0) : 0;      // > 0 here: the window has pixels
+    const int E = window_rows_s(s0, n_events, n_rows);                    // > 0 here: the window has pixels
     const double* ev = events + (size_t)s0 * ev_stride;
     const float* tin = uniq_in + (size_t)b * cap * 8;
     const double* nz = noise_rows ? noise_rows + (size_t)b * kmax * 5 : nullptr;
-    int n = 1;
-    while (n < T) n <<= 1;                                                // T <= cap <= lds_n, a power of two
+    const int n = pow2_at_least(T);                                       // T <= cap <= lds_n, a power of two
     for (int i = tid; i < n; i += EVW_THREADS) {
         unsigned long long k = ~0ull;
-        if (i < M) k = time_key_f64((double)tin[(size_t)i * 8 + 2]);
-        else if (i < T) k = time_key_f64(nz ? nz[(size_t)(i - M) * 5 + 2] : seeded_noise_time(seed, wid, (uint32_t)(i - M), (uint32_t)M, tin));
+        if (i < M) k = time_key((double)tin[(size_t)i * 8 + 2]);
+        else if (i < T) k = time_key(nz ? nz[(size_t)(i - M) * 5 + 2] : seeded_noise_time(seed, wid, (uint32_t)(i - M), (uint32_t)M, tin));
         tkeys[i] = k;
         skeys[i] = (unsigned)i;
     }
     __syncthreads();
-    for (int k2 = 2; k2 <= n; k2 <<= 1) {
-        for (int j = k2 >> 1; j > 0; j >>= 1) {
-            for (int i = tid; i < n; i += EVW_THREADS) {
-                const int ixj = i ^ j;
-                if (ixj > i) {
-                    const unsigned long long ta = tkeys[i], tc = tkeys[ixj];
-                    const unsigned sa = skeys[i], sc = skeys[ixj];
-                    const bool up = (i & k2) == 0;
-                    const bool gt = ta > tc || (ta == tc && sa > sc);
-                    if (gt == up) { tkeys[i] = tc; tkeys[ixj] = ta; skeys[i] = sc; skeys[ixj] = sa; }
-                }
-            }
-            __syncthreads();
-        }
-    }
-    const double tfirst = time_of_key_f64(tkeys[0]);
+    bitonic_sort_lds(n, tid, [=](int i) { return TimeSource{tkeys[i], skeys[i]}; }, [=](int i, TimeSource e) { tkeys[i] = e.t; skeys[i] = e.s; });
+    const double tfirst = time_of_key(tkeys[0]);
     float* tout = uniq_out + (size_t)b * cap * 8;
     for (int j = tid; j < T; j += EVW_THREADS) {
         const int src = (int)skeys[j];
@@ -372,28 +363,26 @@ __global__ __launch_bounds__(EVW_THREADS) void event_window_augment_timesort_ker
             r1.x = q.n_neg;
         }
         // augmented: float64 minus float64, rounded to float32 once (the table is float64 from the concatenation on); otherwise float32
-        r0.z = aug ? (float)__dsub_rn(time_of_key_f64(tkeys[j]), tfirst) : __fsub_rn(r0.z, (float)tfirst);
+        r0.z = aug ? (float)__dsub_rn(time_of_key(tkeys[j]), tfirst) : __fsub_rn(r0.z, (float)tfirst);
         *reinterpret_cast<float4*>(tout + (size_t)j * 8) = r0;
         *reinterpret_cast<float4*>(tout + (size_t)j * 8 + 4) = r1;
         labels_out[(size_t)b * cap + j] = (src < E) ? (int32_t)ev[(size_t)src * ev_stride + label_col] : 3;
     }
 }
 
-__global__ __launch_bounds__(256) void event_window_sample_kernel(const float* __restrict__ uniq, const int32_t* __restrict__ uniq_count, int cap,
-                                                                  const int32_t* __restrict__ sample_idx, int N, int width, int height,
-                                                                  float* __restrict__ out_cm, const int32_t* __restrict__ uniq_labels,
-                                                                  int64_t* __restrict__ out_labels) {
+// The sampler both kernels below run, by a workgroup of 256: index_of(n) = the table row of draw n of window b (asked for twice per
+// draw); the rows' min / max time, then pc_normalize and the [5, N] write, the index into sample_idx_out and the label if wanted.
+template <class IndexOf>
+__device__ __forceinline__ void event_window_sample_body(const float* __restrict__ uniq, int b, int cap, int N, int width, int height,
+                                                         float* __restrict__ out_cm, int32_t* __restrict__ sample_idx_out,
+                                                         const int32_t* __restrict__ uniq_labels, int64_t* __restrict__ out_labels, IndexOf index_of) {
     __shared__ float s_min[256], s_max[256];
-    const int b = blockIdx.x, tid = threadIdx.x;
-    const int M = uniq_count[b];
+    const int tid = threadIdx.x;
     const float* tab = uniq + (size_t)b * cap * 8;
-    const int32_t* idx = sample_idx + (size_t)b * N;
     float* o = out_cm + (size_t)b * 5 * N;
     float mn = INFINITY, mx = -INFINITY;
     for (int n = tid; n < N; n += 256) {
-        int i = idx[n];
-        i = (i < 0 || i >= M || i >= cap) ? 0 : i;
-        const float t = tab[(size_t)i * 8 + 2];
+        const float t = tab[(size_t)index_of(n) * 8 + 2];
         mn = fminf(mn, t);
         mx = fmaxf(mx, t);
     }
@@ -406,8 +395,7 @@ __global__ __launch_bounds__(256) void event_window_sample_kernel(const float* _
     const float tmin = s_min[0], tmax = s_max[0];
     const float range = __fsub_rn(tmax, tmin);
     for (int n = tid; n < N; n += 256) {
-        int i = idx[n];
-        i = (i < 0 || i >= M || i >= cap) ? 0 : i;
+        const int i = index_of(n);
         const float4 r0 = *reinterpret_cast<const float4*>(tab + (size_t)i * 8);
         const float neg = tab[(size_t)i * 8 + 4];
         // pc_normalize: x /= W; y /= H; xy = 2*xy - 1; t = 2*((t - tmin)/(tmax - tmin)) - 1   (float32 ops, no fma)
@@ -416,8 +404,22 @@ __global__ __launch_bounds__(256) void event_window_sample_kernel(const float* _
         o[2 * (size_t)N + n] = __fsub_rn(__fmul_rn(2.f, __fdiv_rn(__fsub_rn(r0.z, tmin), range)), 1.f);
         o[3 * (size_t)N + n] = r0.w;
         o[4 * (size_t)N + n] = neg;
+        if (sample_idx_out) sample_idx_out[(size_t)b * N + n] = i;
         if (out_labels) out_labels[(size_t)b * N + n] = uniq_labels ? (int64_t)uniq_labels[(size_t)b * cap + i] : 0;
     }
+}
+
+__global__ __launch_bounds__(256) void event_window_sample_kernel(const float* __restrict__ uniq, const int32_t* __restrict__ uniq_count, int cap,
+                                                                  const int32_t* __restrict__ sample_idx, int N, int width, int height,
+                                                                  float* __restrict__ out_cm, const int32_t* __restrict__ uniq_labels,
+                                                                  int64_t* __restrict__ out_labels) {
+    const int b = blockIdx.x;
+    const int M = uniq_count[b];
+    const int32_t* idx = sample_idx + (size_t)b * N;
+    event_window_sample_body(uniq, b, cap, N, width, height, out_cm, nullptr, uniq_labels, out_labels, [=](int n) {
+        const int i = idx[n];
+        return (i < 0 || i >= M || i >= cap) ? 0 : i;             // an index outside the table reads row 0
+    });
 }
 
 // event_window_sample_kernel with the index DRAWN here (random.hpp, stream 0) instead of read from memory: draw n of window
@@ -429,7 +431,6 @@ __global__ __launch_bounds__(256) void event_window_sample_seeded_kernel(const f
                                                                          int width, int height, float* __restrict__ out_cm,
                                                                          int32_t* __restrict__ sample_idx_out, const int32_t* __restrict__ uniq_labels,
                                                                          int64_t* __restrict__ out_labels, int32_t* __restrict__ status) {
-    __shared__ float s_min[256], s_max[256];
     const int b = blockIdx.x, tid = threadIdx.x;
     const int M = uniq_count[b];
     const int32_t wid = window_ids[b];
@@ -444,47 +445,49 @@ __global__ __launch_bounds__(256) void event_window_sample_seeded_kernel(const f
         }
         return;
     }
-    const float* tab = uniq + (size_t)b * cap * 8;
-    float mn = INFINITY, mx = -INFINITY;
-    for (int n = tid; n < N; n += 256) {
-        const int i = ev2h_random::sample_index(seed, (uint32_t)wid, (uint32_t)n, (uint32_t)M);
-        const float t = tab[(size_t)i * 8 + 2];
-        mn = fminf(mn, t);
-        mx = fmaxf(mx, t);
-    }
-    s_min[tid] = mn; s_max[tid] = mx;
-    __syncthreads();
-    for (int off = 128; off > 0; off >>= 1) {
-        if (tid < off) { s_min[tid] = fminf(s_min[tid], s_min[tid + off]); s_max[tid] = fmaxf(s_max[tid], s_max[tid + off]); }
-        __syncthreads();
-    }
-    const float tmin = s_min[0], tmax = s_max[0];
-    const float range = __fsub_rn(tmax, tmin);
-    for (int n = tid; n < N; n += 256) {
-        const int i = ev2h_random::sample_index(seed, (uint32_t)wid, (uint32_t)n, (uint32_t)M);      // drawn again: cheaper than keeping N indices
-        const float4 r0 = *reinterpret_cast<const float4*>(tab + (size_t)i * 8);
-        const float neg = tab[(size_t)i * 8 + 4];
-        o[0 * (size_t)N + n] = __fsub_rn(__fmul_rn(2.f, __fdiv_rn(r0.x, (float)width)), 1.f);
-        o[1 * (size_t)N + n] = __fsub_rn(__fmul_rn(2.f, __fdiv_rn(r0.y, (float)height)), 1.f);
-        o[2 * (size_t)N + n] = __fsub_rn(__fmul_rn(2.f, __fdiv_rn(__fsub_rn(r0.z, tmin), range)), 1.f);
-        o[3 * (size_t)N + n] = r0.w;
-        o[4 * (size_t)N + n] = neg;
-        if (sample_idx_out) sample_idx_out[(size_t)b * N + n] = i;
-        if (out_labels) out_labels[(size_t)b * N + n] = uniq_labels ? (int64_t)uniq_labels[(size_t)b * cap + i] : 0;
-    }
+    // the body asks for every index twice: drawing again is cheaper than keeping N indices
+    event_window_sample_body(uniq, b, cap, N, width, height, out_cm, sample_idx_out, uniq_labels, out_labels,
+                             [=](int n) { return ev2h_random::sample_index(seed, (uint32_t)wid, (uint32_t)n, (uint32_t)M); });
+}
+
+// what every build entry point asks of the sensor, the event rows and the table it fills
+int check_build_args(const double* events, int ev_stride, int B, int width, int height, int cap, const int32_t* uniq_count, const float* uniq) {
+    EV2H_CHECK_ARG(width > 0 && height > 0 && (long long)width * height <= EVW_MAX_PIXELS);
+    EV2H_CHECK_ARG(events && uniq_count && uniq && ev_stride >= 4 && B > 0 && cap > 0);
+    return EV2H_OK;
+}
+
+// raise KERNEL's dynamic-LDS limit to `bytes`, once per device
+template <auto KERNEL>
+int raise_dynamic_lds(int bytes) {
+    static PerDevice done{};
+    EV2H_ONCE_PER_DEVICE(done, EV2H_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(KERNEL), hipFuncAttributeMaxDynamicSharedMemorySize, bytes)););
+    return EV2H_OK;
+}
+
+// the first half of both ev2h_event_window_build_s_ranges*: their shared checks (max_cap: what the time sort that follows holds) and
+// the unsorted tables
+int build_s_ranges(const double* events, int ev_stride, int n_rows, const int32_t* starts, int B, int n_events, int width, int height, int cap,
+                   int max_cap, int anno_col, int label_col, int32_t* uniq_count, float* uniq_scratch, float* uniq_sorted, int32_t* labels,
+                   int32_t* annotation, ev2h_stream_t stream) {
+    if (const int rc = check_build_args(events, ev_stride, B, width, height, cap, uniq_count, uniq_scratch)) return rc;
+    EV2H_CHECK_ARG(starts && uniq_sorted && labels && annotation && uniq_scratch != uniq_sorted);
+    EV2H_CHECK_ARG(n_rows > 0 && n_events > 0 && n_events <= EVW_MAX_EVENTS && cap <= max_cap);
+    EV2H_CHECK_ARG(anno_col >= 0 && anno_col < ev_stride && label_col >= 0 && label_col < ev_stride);
+    if (const int rc = raise_dynamic_lds<event_window_build_s_ranges_kernel>(EVW_MAX_EVENTS * 4)) return rc;
+    event_window_build_s_ranges_kernel<<<B, EVW_THREADS, EVW_MAX_EVENTS * 4, (hipStream_t)stream>>>(events, ev_stride, n_rows, starts, n_events, width, height,
+                                                                                                    cap, anno_col, uniq_count, uniq_scratch, annotation);
+    EV2H_CHECK_LAUNCH();
+    return EV2H_OK;
 }
 
 }  // namespace
 
 extern "C" int ev2h_event_window_build(const double* events, int ev_stride, const int32_t* offsets, int B, int width, int height, int cap,
                                        int raw_time, int32_t* uniq_count, float* uniq, ev2h_stream_t stream) {
-    EV2H_CHECK_ARG(width > 0 && height > 0 && (long long)width * height <= EVW_MAX_PIXELS);
-    EV2H_CHECK_ARG(events && offsets && uniq_count && uniq && ev_stride >= 4);
-    EV2H_CHECK_ARG(B > 0 && cap > 0);
-    static PerDevice attr_set{};
-    EV2H_ONCE_PER_DEVICE(attr_set,
-        EV2H_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(event_window_build_kernel),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, EVW_MAX_EVENTS * 4)););
+    if (const int rc = check_build_args(events, ev_stride, B, width, height, cap, uniq_count, uniq)) return rc;
+    EV2H_CHECK_ARG(offsets);
+    if (const int rc = raise_dynamic_lds<event_window_build_kernel>(EVW_MAX_EVENTS * 4)) return rc;
     event_window_build_kernel<<<B, EVW_THREADS, EVW_MAX_EVENTS * 4, (hipStream_t)stream>>>(events, offsets, width, height, cap, raw_time, ev_stride, uniq_count, uniq);
     EV2H_CHECK_LAUNCH();
     return EV2H_OK;
@@ -493,13 +496,9 @@ extern "C" int ev2h_event_window_build(const double* events, int ev_stride, cons
 extern "C" int ev2h_event_window_build_ranges(const double* events, int ev_stride, int n_rows, const int32_t* starts, const int32_t* ends, int B,
                                               int width, int height, int cap, int frame_col, int32_t* uniq_count, float* uniq,
                                               int32_t* frame_index, int32_t* first_frame, ev2h_stream_t stream) {
-    EV2H_CHECK_ARG(width > 0 && height > 0 && (long long)width * height <= EVW_MAX_PIXELS);
-    EV2H_CHECK_ARG(events && starts && ends && uniq_count && uniq && frame_index && first_frame && ev_stride >= 4 && n_rows > 0);
-    EV2H_CHECK_ARG(B > 0 && cap > 0 && frame_col < ev_stride);
-    static PerDevice attr_set{};
-    EV2H_ONCE_PER_DEVICE(attr_set,
-        EV2H_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(event_window_build_ranges_kernel),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, EVW_MAX_EVENTS * 4)););
+    if (const int rc = check_build_args(events, ev_stride, B, width, height, cap, uniq_count, uniq)) return rc;
+    EV2H_CHECK_ARG(starts && ends && frame_index && first_frame && n_rows > 0 && frame_col < ev_stride);
+    if (const int rc = raise_dynamic_lds<event_window_build_ranges_kernel>(EVW_MAX_EVENTS * 4)) return rc;
     event_window_build_ranges_kernel<<<B, EVW_THREADS, EVW_MAX_EVENTS * 4, (hipStream_t)stream>>>(events, ev_stride, n_rows, starts, ends, width, height, cap,
                                                                                                   frame_col, uniq_count, uniq, frame_index, first_frame);
     EV2H_CHECK_LAUNCH();
@@ -511,10 +510,7 @@ extern "C" int ev2h_event_window_timesort(const float* uniq_in, const int32_t* u
                                           ev2h_stream_t stream) {
     EV2H_CHECK_ARG(uniq_in && uniq_count && uniq_out && uniq_in != uniq_out && B > 0 && cap > 0 && cap <= EVS_MAX);
     EV2H_CHECK_ARG(!labels_out || !events || (offsets && ev_stride > label_col && label_col >= 0));
-    static PerDevice attr_set{};
-    EV2H_ONCE_PER_DEVICE(attr_set,
-        EV2H_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(event_window_timesort_kernel),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, EVS_MAX * 8)););
+    if (const int rc = raise_dynamic_lds<event_window_timesort_kernel>(EVS_MAX * 8)) return rc;
     event_window_timesort_kernel<<<B, EVW_THREADS, EVS_MAX * 8, (hipStream_t)stream>>>(uniq_in, uniq_count, cap, events, ev_stride, label_col,
                                                                                        offsets, uniq_out, labels_out);
     EV2H_CHECK_LAUNCH();
@@ -525,17 +521,8 @@ extern "C" int ev2h_event_window_build_s_ranges(const double* events, int ev_str
                                                 int width, int height, int cap, int anno_col, int label_col, int32_t* uniq_count,
                                                 float* uniq_scratch, float* uniq_sorted, int32_t* labels, int32_t* annotation,
                                                 ev2h_stream_t stream) {
-    EV2H_CHECK_ARG(width > 0 && height > 0 && (long long)width * height <= EVW_MAX_PIXELS);
-    EV2H_CHECK_ARG(events && starts && uniq_count && uniq_scratch && uniq_sorted && labels && annotation && uniq_scratch != uniq_sorted);
-    EV2H_CHECK_ARG(B > 0 && n_rows > 0 && n_events > 0 && n_events <= EVW_MAX_EVENTS && cap > 0 && cap <= EVS_MAX);
-    EV2H_CHECK_ARG(ev_stride >= 4 && anno_col >= 0 && anno_col < ev_stride && label_col >= 0 && label_col < ev_stride);
-    static PerDevice attr_set{};
-    EV2H_ONCE_PER_DEVICE(attr_set,
-        EV2H_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(event_window_build_s_ranges_kernel),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, EVW_MAX_EVENTS * 4)););
-    event_window_build_s_ranges_kernel<<<B, EVW_THREADS, EVW_MAX_EVENTS * 4, (hipStream_t)stream>>>(events, ev_stride, n_rows, starts, n_events, width, height,
-                                                                                                    cap, anno_col, uniq_count, uniq_scratch, annotation);
-    EV2H_CHECK_LAUNCH();
+    if (const int rc = build_s_ranges(events, ev_stride, n_rows, starts, B, n_events, width, height, cap, EVS_MAX, anno_col, label_col, uniq_count,
+                                      uniq_scratch, uniq_sorted, labels, annotation, stream)) return rc;
     // the time sort reads offsets[b] only, i.e. the window's first row: `starts` as they are.  An empty window has count 0 and is skipped there.
     return ev2h_event_window_timesort(uniq_scratch, uniq_count, cap, events, ev_stride, label_col, starts, B, uniq_sorted, labels, stream);
 }
@@ -545,24 +532,13 @@ extern "C" int ev2h_event_window_build_s_ranges_aug(const double* events, int ev
                                                     const int32_t* noise_n, int noise_kmax, uint64_t seed, const int32_t* window_ids,
                                                     int32_t* uniq_count, float* uniq_scratch, float* uniq_sorted, int32_t* labels,
                                                     int32_t* annotation, int32_t* coin, ev2h_stream_t stream) {
-    EV2H_CHECK_ARG(width > 0 && height > 0 && (long long)width * height <= EVW_MAX_PIXELS);
-    EV2H_CHECK_ARG(events && starts && uniq_count && uniq_scratch && uniq_sorted && labels && annotation && uniq_scratch != uniq_sorted);
-    EV2H_CHECK_ARG(B > 0 && n_rows > 0 && n_events > 0 && n_events <= EVW_MAX_EVENTS && cap > 0 && cap <= EVA_MAX);
-    EV2H_CHECK_ARG(ev_stride >= 4 && anno_col >= 0 && anno_col < ev_stride && label_col >= 0 && label_col < ev_stride);
     // exactly one source of noise: the caller's rows, or the seeded draw
     EV2H_CHECK_ARG((noise_rows != nullptr) == (noise_n != nullptr) && (noise_n != nullptr) != (window_ids != nullptr));
     EV2H_CHECK_ARG(!noise_rows || noise_kmax > 0);
-    static PerDevice attr_set{};
-    EV2H_ONCE_PER_DEVICE(attr_set,
-        EV2H_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(event_window_build_s_ranges_kernel),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, EVW_MAX_EVENTS * 4));
-        EV2H_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(event_window_augment_timesort_kernel),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, EVA_MAX * 12)););
-    event_window_build_s_ranges_kernel<<<B, EVW_THREADS, EVW_MAX_EVENTS * 4, (hipStream_t)stream>>>(events, ev_stride, n_rows, starts, n_events, width, height,
-                                                                                                    cap, anno_col, uniq_count, uniq_scratch, annotation);
-    EV2H_CHECK_LAUNCH();
-    int lds_n = 1;
-    while (lds_n < cap) lds_n <<= 1;
+    if (const int rc = raise_dynamic_lds<event_window_augment_timesort_kernel>(EVA_MAX * 12)) return rc;
+    if (const int rc = build_s_ranges(events, ev_stride, n_rows, starts, B, n_events, width, height, cap, EVA_MAX, anno_col, label_col, uniq_count,
+                                      uniq_scratch, uniq_sorted, labels, annotation, stream)) return rc;
+    const int lds_n = pow2_at_least(cap);
     event_window_augment_timesort_kernel<<<B, EVW_THREADS, (size_t)lds_n * 12, (hipStream_t)stream>>>(
         uniq_scratch, uniq_count, cap, lds_n, events, ev_stride, n_rows, label_col, starts, n_events, noise_rows, noise_n, noise_kmax,
         (unsigned long long)seed, window_ids, width, height, uniq_sorted, labels, coin);

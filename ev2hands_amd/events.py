@@ -14,8 +14,10 @@ import numpy as np
 import torch
 
 from . import _lib
+from ._lib import _dev_tensor
 
 OUTPUT_WIDTH, OUTPUT_HEIGHT = 346, 260       # /root/reference/src/settings.py:21-22
+_NO_WINDOW = 2 ** 31 - 1                     # a `status` while every window could be sampled (the kernels lower it with atomicMin)
 
 
 class EventWindowBuilder:
@@ -52,8 +54,8 @@ class EventWindowBuilder:
         if self.raw_time:
             raise RuntimeError("accumulate_ranges builds evaluation windows (timestamps minus the window's first)")
         B = int(starts.shape[0])
-        if int(ends.shape[0]) != B or starts.dtype != torch.int32 or ends.dtype != torch.int32 or not (starts.is_contiguous() and ends.is_contiguous()):
-            raise ValueError("starts and ends must be contiguous int32 device tensors of one length")
+        for t, name in ((starts, "starts"), (ends, "ends")):
+            _dev_tensor(t, name, torch.int32, (B,), stream.events.device)
         if out is None:
             out = (torch.empty(B, self.cap, 8, device=self.device, dtype=torch.float32), torch.empty(B, device=self.device, dtype=torch.int32),
                    torch.empty(B, device=self.device, dtype=torch.int32), torch.empty(B, device=self.device, dtype=torch.int32))
@@ -73,10 +75,7 @@ class EventWindowBuilder:
         row 0 for every index outside [0, min(M, cap))."""
         B = table.shape[0]
         if sample_idx is None:
-            ms = counts.cpu().numpy()
-            if (ms <= 0).any() or (ms > self.cap).any():          # the table holds `cap` rows: an index drawn from [0, M) beyond them would read row 0
-                raise RuntimeError("an event window is empty, exceeds 32768 events or has more unique pixels than `cap`")
-            sample_idx = np.stack([np.random.choice(int(m), self.n) for m in ms])
+            sample_idx = self._draw(counts, "an event window is empty, exceeds 32768 events or has more unique pixels than `cap`")
         idx = torch.as_tensor(np.asarray(sample_idx), dtype=torch.int32).to(self.device).contiguous()
         n = idx.shape[1]
         out = torch.empty(B, 5, n, device=self.device, dtype=torch.float32)
@@ -86,6 +85,27 @@ class EventWindowBuilder:
                                               self.h, out.data_ptr(), _lib.ptr(labels), _lib.ptr(lab), _lib.stream_handle()),
                    "ev2h_event_window_sample")
         return out if labels is None else (out, lab)
+
+    def _draw(self, counts, error: str, given=None, pad: bool = False) -> np.ndarray:
+        """The windows' resampling indices [B, N] the way the reference draws them.  The counts come to the host (one small copy) and
+        `error` is raised unless every window has 1 .. cap pixels (the table holds `cap` rows: an index drawn from [0, M) beyond
+        them would read row 0).  Then `given` as it is, or np.random.choice(M_b, N) per window in batch order from numpy's global
+        generator.  pad (erpc.py:220-227): all M_b pixels, then N - M_b resampled ones -- given[b], or np.random.choice(M_b, N - M_b)."""
+        ms = counts.cpu().numpy()
+        if (ms <= 0).any() or (ms > self.cap).any():
+            raise RuntimeError(error)
+        if not pad:
+            return given if given is not None else np.stack([np.random.choice(int(m), self.n) for m in ms])
+        if (ms > self.n).any():                                   # n raw events give M <= n pixels
+            raise RuntimeError("sampling=False needs at most n_events unique pixels per window")
+        rows = []
+        for b, m in enumerate(int(v) for v in ms):
+            if m == self.n:
+                extra = np.zeros(0, dtype=np.int64)
+            else:
+                extra = np.asarray(given[b], dtype=np.int64) if given is not None else np.random.choice(m, self.n - m)
+            rows.append(np.concatenate([np.arange(m, dtype=np.int64), extra]))
+        return np.stack(rows)
 
     def sample_seeded(self, table, counts, seed: int, window_ids, labels=None, return_idx: bool = False, status=None, out=None, labels_out=None):
         """`sample` with the indices drawn on the device by a counter-based generator (csrc/random.hpp) instead of
@@ -99,25 +119,22 @@ class EventWindowBuilder:
         labels into (with `labels`).
         -> events [B, 5, N] (, labels [B, N] int64 with `labels`) (, the indices [B, N] int32 with return_idx)."""
         B = int(table.shape[0])
-        if window_ids.dtype != torch.int32 or window_ids.device != table.device or not window_ids.is_contiguous() or tuple(window_ids.shape) != (B,):
-            raise ValueError("window_ids must be a contiguous int32 device tensor [B]")
+        _dev_tensor(window_ids, "window_ids", torch.int32, (B,), table.device)
         if not 0 <= int(seed) < 2 ** 64:
             raise ValueError("seed must be an unsigned 64-bit integer")
         own_status = status is None
         if own_status:
-            status = torch.full((1,), 2 ** 31 - 1, device=self.device, dtype=torch.int32)
+            status = torch.full((1,), _NO_WINDOW, device=self.device, dtype=torch.int32)
         elif status.dtype != torch.int32 or status.device != table.device or status.numel() != 1:
             raise ValueError("status must be a device int32 tensor with one element")
         n = self.n
         if out is None:
             out = torch.empty(B, 5, n, device=self.device, dtype=torch.float32)
-        elif tuple(out.shape) != (B, 5, n) or out.dtype != torch.float32 or not out.is_contiguous():
-            raise ValueError(f"out must be a contiguous float32 [{B}, 5, {n}] tensor")
+        _dev_tensor(out, "out", torch.float32, (B, 5, n), table.device)
         lab = None
         if labels is not None:
             lab = torch.empty(B, n, device=self.device, dtype=torch.int64) if labels_out is None else labels_out
-            if tuple(lab.shape) != (B, n) or lab.dtype != torch.int64 or lab.device != table.device or not lab.is_contiguous():
-                raise ValueError(f"labels_out must be a contiguous int64 [{B}, {n}] device tensor")
+            _dev_tensor(lab, "labels_out", torch.int64, (B, n), table.device)
         idx = torch.empty(B, n, device=self.device, dtype=torch.int32) if return_idx is True else (return_idx if torch.is_tensor(return_idx) else None)
         if B:
             _lib.check(_lib.lib().ev2h_event_window_sample_seeded(table.data_ptr(), counts.data_ptr(), self.cap, int(seed), window_ids.data_ptr(), B, n,
@@ -125,7 +142,7 @@ class EventWindowBuilder:
                                                                   status.data_ptr(), _lib.stream_handle()), "ev2h_event_window_sample_seeded")
         if own_status:
             bad = int(status.item())
-            if bad != 2 ** 31 - 1:
+            if bad != _NO_WINDOW:
                 raise RuntimeError(f"window {bad} is empty, exceeds 32768 events or has more unique pixels than `cap`")
         res = (out,) + ((lab,) if labels is not None else ()) + ((idx,) if idx is not None else ())
         return res[0] if len(res) == 1 else res
@@ -203,59 +220,49 @@ class EventWindowBuilderS(EventWindowBuilder):
         augmented.  With neither argument this is the plain call, unchanged."""
         if not isinstance(table, EventTableS):
             raise TypeError("EventWindowBuilderS.accumulate_ranges takes an EventTableS")
-        B = int(starts.shape[0])
-        if starts.dim() != 1 or starts.dtype != torch.int32 or not starts.is_contiguous() or starts.device != table.events.device:
-            raise ValueError("starts must be a contiguous int32 tensor [B] on the table's device")
-        dev = table.events.device
-        f32, i32 = dict(device=dev, dtype=torch.float32), dict(device=dev, dtype=torch.int32)
+        if noise is not None and augment is not None:
+            raise ValueError("give `noise` or `augment`, not both")
+        augmented = noise is not None or augment is not None
+        if augmented and self.cap > 8192:
+            raise ValueError("the augmented time sort holds at most 8192 rows per window: cap <= 8192")
+        if coin is not None and not augmented:
+            raise ValueError("`coin` goes with `noise` or `augment`")
+        B, cap, dev = int(starts.shape[0]), self.cap, table.events.device
+        f32, f64, i32 = torch.float32, torch.float64, torch.int32
         if out is None:
-            out = (torch.empty(B, self.cap, 8, **f32), torch.empty(B, **i32), torch.zeros(B, self.cap, **i32), torch.empty(B, **i32))
+            out = (torch.empty(B, cap, 8, device=dev, dtype=f32), torch.empty(B, device=dev, dtype=i32), torch.zeros(B, cap, device=dev, dtype=i32),
+                   torch.empty(B, device=dev, dtype=i32))
         sorted_t, counts, labels, annotation = out
         if scratch is None:
-            scratch = torch.empty(B, self.cap, 8, **f32)
-        for t, shape, dt, name in ((sorted_t, (B, self.cap, 8), torch.float32, "sorted table"), (scratch, (B, self.cap, 8), torch.float32, "scratch"),
-                                   (counts, (B,), torch.int32, "counts"), (labels, (B, self.cap), torch.int32, "labels"),
-                                   (annotation, (B,), torch.int32, "annotation")):
-            if tuple(t.shape) != shape or t.dtype != dt or t.device != dev or not t.is_contiguous():
-                raise ValueError(f"{name} must be a contiguous {dt} tensor {list(shape)} on {dev}")
-        if noise is not None or augment is not None:
-            if noise is not None and augment is not None:
-                raise ValueError("give `noise` or `augment`, not both")
-            if self.cap > 8192:
-                raise ValueError("the augmented time sort holds at most 8192 rows per window: cap <= 8192")
-            rows = n = ids = None
-            seed, kmax = 0, 0
-            if noise is not None:
-                rows, n = noise
-                rows = (rows if torch.is_tensor(rows) else torch.from_numpy(np.ascontiguousarray(rows, dtype=np.float64))).to(dev)
-                n = (n if torch.is_tensor(n) else torch.from_numpy(np.ascontiguousarray(n, dtype=np.int32))).to(dev)
-                if rows.dim() != 3 or rows.shape[0] != B or rows.shape[2] != 5 or rows.shape[1] < 1 or rows.dtype != torch.float64 or not rows.is_contiguous():
-                    raise ValueError(f"noise rows must be a contiguous float64 [{B}, Kmax >= 1, 5] tensor")
-                if tuple(n.shape) != (B,) or n.dtype != torch.int32 or not n.is_contiguous():
-                    raise ValueError(f"noise counts must be a contiguous int32 [{B}] tensor")
-                kmax = int(rows.shape[1])
-            else:
-                seed, ids = augment
-                if not 0 <= int(seed) < 2 ** 64:
-                    raise ValueError("seed must be an unsigned 64-bit integer")
-                if not torch.is_tensor(ids) or ids.dtype != torch.int32 or ids.device != dev or not ids.is_contiguous() or tuple(ids.shape) != (B,):
-                    raise ValueError("window_ids must be a contiguous int32 device tensor [B]")
-            if coin is not None and (tuple(coin.shape) != (B,) or coin.dtype != torch.int32 or coin.device != dev or not coin.is_contiguous()):
-                raise ValueError(f"coin must be a contiguous int32 [{B}] tensor on {dev}")
-            if B:
-                _lib.check(_lib.lib().ev2h_event_window_build_s_ranges_aug(table.events.data_ptr(), table.stride, table.n_rows, starts.data_ptr(), B, self.n,
-                                                                           self.w, self.h, self.cap, EventTableS.ANNOTATION_COL, EventTableS.LABEL_COL,
-                                                                           _lib.ptr(rows), _lib.ptr(n), kmax, int(seed), _lib.ptr(ids), counts.data_ptr(),
-                                                                           scratch.data_ptr(), sorted_t.data_ptr(), labels.data_ptr(), annotation.data_ptr(),
-                                                                           _lib.ptr(coin), _lib.stream_handle()), "ev2h_event_window_build_s_ranges_aug")
-            return sorted_t, counts, labels, annotation
+            scratch = torch.empty(B, cap, 8, device=dev, dtype=f32)
+        contract = [(starts, "starts", i32, (B,)), (sorted_t, "sorted table", f32, (B, cap, 8)), (scratch, "scratch", f32, (B, cap, 8)),
+                    (counts, "counts", i32, (B,)), (labels, "labels", i32, (B, cap)), (annotation, "annotation", i32, (B,))]
+        rows = n = ids = None
+        seed, kmax = 0, 0
+        if noise is not None:
+            rows, n = noise
+            rows = (rows if torch.is_tensor(rows) else torch.from_numpy(np.ascontiguousarray(rows, dtype=np.float64))).to(dev)
+            n = (n if torch.is_tensor(n) else torch.from_numpy(np.ascontiguousarray(n, dtype=np.int32))).to(dev)
+            kmax = max(int(rows.shape[1]), 1) if rows.dim() == 3 else 1                 # [B, Kmax >= 1, 5]
+            contract += [(rows, "noise rows", f64, (B, kmax, 5)), (n, "noise counts", i32, (B,))]
+        elif augment is not None:
+            seed, ids = augment
+            if not 0 <= int(seed) < 2 ** 64:
+                raise ValueError("seed must be an unsigned 64-bit integer")
+            contract.append((ids, "window_ids", i32, (B,)))
         if coin is not None:
-            raise ValueError("`coin` goes with `noise` or `augment`")
-        if B:
-            _lib.check(_lib.lib().ev2h_event_window_build_s_ranges(table.events.data_ptr(), table.stride, table.n_rows, starts.data_ptr(), B, self.n,
-                                                                   self.w, self.h, self.cap, EventTableS.ANNOTATION_COL, EventTableS.LABEL_COL,
-                                                                   counts.data_ptr(), scratch.data_ptr(), sorted_t.data_ptr(), labels.data_ptr(),
-                                                                   annotation.data_ptr(), _lib.stream_handle()), "ev2h_event_window_build_s_ranges")
+            contract.append((coin, "coin", i32, (B,)))
+        for t, name, dt, shape in contract:
+            _dev_tensor(t, name, dt, shape, dev)
+        args = (table.events.data_ptr(), table.stride, table.n_rows, starts.data_ptr(), B, self.n, self.w, self.h, cap, EventTableS.ANNOTATION_COL,
+                EventTableS.LABEL_COL)
+        outs = (counts.data_ptr(), scratch.data_ptr(), sorted_t.data_ptr(), labels.data_ptr(), annotation.data_ptr())
+        if B and augmented:
+            _lib.check(_lib.lib().ev2h_event_window_build_s_ranges_aug(*args, _lib.ptr(rows), _lib.ptr(n), kmax, int(seed),
+                                                                       _lib.ptr(ids), *outs, _lib.ptr(coin), _lib.stream_handle()),
+                       "ev2h_event_window_build_s_ranges_aug")
+        elif B:
+            _lib.check(_lib.lib().ev2h_event_window_build_s_ranges(*args, *outs, _lib.stream_handle()), "ev2h_event_window_build_s_ranges")
         return sorted_t, counts, labels, annotation
 
     def __call__(self, windows, sampling: bool = True, sample_idx=None):
@@ -268,25 +275,7 @@ class EventWindowBuilderS(EventWindowBuilder):
         _lib.check(L.ev2h_event_window_timesort(table.data_ptr(), counts.data_ptr(), self.cap, ev.data_ptr(), ev.shape[1], 5,
                                                 off.data_ptr(), B, sorted_t.data_ptr(), labels.data_ptr(), _lib.stream_handle()),
                    "ev2h_event_window_timesort")
-        ms = counts.cpu().numpy()
-        if (ms <= 0).any() or (ms > self.cap).any():
-            raise RuntimeError("an event window is empty or has more unique pixels than `cap`")
-        if sampling:
-            idx = sample_idx if sample_idx is not None else np.stack([np.random.choice(int(m), self.n) for m in ms])
-        else:
-            # erpc.py:220-227: keep all M pixels and append n_events - M resampled ones (n raw events give M <= n pixels)
-            if (ms > self.n).any():
-                raise RuntimeError("sampling=False needs at most n_events unique pixels per window")
-            rows = []
-            for b, m in enumerate(int(v) for v in ms):
-                if m == self.n:
-                    extra = np.zeros(0, dtype=np.int64)
-                elif sample_idx is not None:
-                    extra = np.asarray(sample_idx[b], dtype=np.int64)
-                else:
-                    extra = np.random.choice(m, self.n - m)
-                rows.append(np.concatenate([np.arange(m, dtype=np.int64), extra]))
-            idx = np.stack(rows)
+        idx = self._draw(counts, "an event window is empty or has more unique pixels than `cap`", sample_idx, pad=not sampling)
         events, lab = self.sample(sorted_t, counts, idx, labels)
         self.table, self.table_labels = sorted_t, labels
         return {"events": events, "class_logits": lab}

@@ -27,8 +27,9 @@ import numpy as np
 import torch
 
 from . import _lib
+from ._lib import _dev_tensor
 from .collision import CollisionLoss, device_faces
-from .metrics import _dev_tensor, segmentation_score
+from .metrics import segmentation_score
 
 NT, NSTATE = _lib.LOSS_NT, _lib.LOSS_NSTATE
 _M_INTER, _M_LEFT, _M_RIGHT, _M_ALL = 0, 1, 2, 3          # a term's denominator: count of (interacting, valid_left, valid_right, windows) * D

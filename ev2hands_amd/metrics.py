@@ -10,6 +10,7 @@ import numpy as np
 import torch
 
 from . import _lib
+from ._lib import _dev_tensor
 
 
 def evaluate_joints_real_batch(j3d_left: torch.Tensor, j3d_right: torch.Tensor, j3d_gts: torch.Tensor, num_steps: int,
@@ -61,14 +62,6 @@ def evaluate_joints_real_batch(j3d_left: torch.Tensor, j3d_right: torch.Tensor, 
 
 
 # ----------------------------------------------------------------------------- the synthetic test set's scorers (csrc/metrics_s.hip)
-def _dev_tensor(t, name, dtype, shape, dev=None, contiguous=True):
-    if not isinstance(t, torch.Tensor) or t.dtype != dtype or tuple(t.shape) != tuple(shape) or t.device.type != "cuda" \
-            or (dev is not None and t.device != dev) or (contiguous and not t.is_contiguous()):
-        raise ValueError(f"{name} must be a {'contiguous ' if contiguous else ''}{dtype} tensor {list(shape)} on "
-                         f"{dev if dev is not None else 'a CUDA device'}, got {getattr(t, 'dtype', type(t))} {list(getattr(t, 'shape', ()))} "
-                         f"on {getattr(t, 'device', None)}")
-
-
 def joint_metrics_f32_frames(j3d_left: torch.Tensor, j3d_right: torch.Tensor, joints_gt: torch.Tensor, annotation: torch.Tensor,
                              num_steps: int = 50, dist_max_mm: float = 50.0, out=None):
     """The three PCK curves as evaluate.py: evaluate_net computes them (:273-293 with :185-234), float32 throughout, for B windows on

@@ -18,10 +18,9 @@ from __future__ import annotations
 
 import torch
 
+from ._lib import _dev_tensor
 from .evaluate import annotation_flags, annotation_table
-from .events import OUTPUT_HEIGHT, OUTPUT_WIDTH, EventTableS, EventWindowBuilderS
-
-_NO_WINDOW = 2 ** 31 - 1
+from .events import _NO_WINDOW, OUTPUT_HEIGHT, OUTPUT_WIDTH, EventTableS, EventWindowBuilderS
 
 
 class TrainingBatcherS:
@@ -81,8 +80,7 @@ class TrainingBatcherS:
         if not 1 <= B <= self.max_batch:
             raise ValueError(f"a batch holds 1 .. {self.max_batch} windows")
         for t, name in ((starts, "starts"), (window_ids, "window_ids")):
-            if not torch.is_tensor(t) or tuple(t.shape) != (B,) or t.dtype != torch.int32 or t.device != self.device or not t.is_contiguous():
-                raise ValueError(f"{name} must be a contiguous int32 tensor [B] on {self.device}")
+            _dev_tensor(t, name, torch.int32, (B,), self.device)
         bld, K = self.builder, self.n_pose
         out = tuple(t[:B] for t in self._out)
         coin = self._coin[:B]

@@ -120,3 +120,39 @@ def test_finish_reports_a_stop_an_unsampled_window_and_an_empty_run():
     assert got["frame_index"] == 1 and got["joint_loss"] == 0.0 and got["non_collision_score"] == [] and got["auc"]["relative"] == 0.0
     with pytest.raises(RuntimeError, match="no frame"):
         finish_metrics(empty, 3076, reference_quirks=False)
+
+
+RECORDING_OFFSETS = {"sums": (0, 128), "joint_loss": (128, 24), "root_distance": (152, 24), "auc": (176, 72), "collision_count": (248, 12),
+                     "frame_index": (264, 12), "scalars": (280, 8), "status": (288, 4)}
+SYNTHETIC_OFFSETS = {"sums": (0, 136), "confusion": (136, 136), "auc": (272, 72), "l1": (344, 24), "ce_num_w": (368, 24), "ce_den_w": (392, 24),
+                     "annotation": (416, 12), "scalars": (432, 8), "status": (440, 4)}
+LOSS_OFFSETS = {"loss_state": (448, 216), "loss_scalars": (664, 8)}
+
+
+@pytest.mark.parametrize("which,offsets,total", [("recording", RECORDING_OFFSETS, 296), ("synthetic", SYNTHETIC_OFFSETS, 448),
+                                                 ("synthetic+loss", {**SYNTHETIC_OFFSETS, **LOSS_OFFSETS}, 672)])
+def test_state_blob_layout_views_and_host_copy(which, offsets, total):
+    """W = 3 windows, num_steps = 4: the (offset, bytes) of every field are the ones the accumulate kernels have always been handed,
+    every view is a window of the one allocation, and host() returns what was written through the views"""
+    import torch
+    from ev2hands_amd.evaluate import _StateBlob, _recording_fields, _synthetic_fields
+    fields = _recording_fields(3, 5) if which == "recording" else _synthetic_fields(3, 5, loss_state=which.endswith("loss"))
+    sb = _StateBlob("cpu", fields)
+    assert [f[0] for f in fields] == list(offsets) == list(sb.layout) == list(sb.state)
+    assert {k: v[:2] for k, v in sb.layout.items()} == offsets
+    assert sb.blob.dtype == torch.uint8 and sb.blob.numel() == total
+    base = sb.blob.data_ptr()
+    r = np.random.RandomState(5)
+    written = {}
+    for name, (off, nb, dt, shape) in sb.layout.items():
+        v = sb.state[name]
+        assert v.data_ptr() == base + off and off % 8 == 0 and v.dtype == dt and tuple(v.shape) == tuple(shape) and v.numel() * v.element_size() == nb
+        start = [0, -1] if name.endswith("scalars") else [2 ** 31 - 1] if name == "status" else [0] * v.numel()
+        assert v.reshape(-1).tolist() == start, name
+        written[name] = r.randint(-99, 99, shape)
+        v.copy_(torch.from_numpy(written[name]).to(dt))
+    host = sb.host()
+    assert list(host) == list(offsets)
+    for name, arr in host.items():
+        want = {torch.float64: np.float64, torch.int64: np.int64, torch.int32: np.int32}[sb.layout[name][2]]
+        assert arr.dtype == want and arr.shape == tuple(sb.layout[name][3]) and np.array_equal(arr, written[name]), name

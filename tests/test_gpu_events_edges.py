@@ -376,6 +376,31 @@ def test_sampler_index_edges(dev, N):
         assert set(np.unique(plain[2][2])) == {-1.0, 1.0} and np.isfinite(plain[3]).all()
 
 
+@pytest.mark.parametrize("N", [1, 255, 257])
+def test_seeded_and_explicit_sampler_are_one_body(dev, N):
+    """the seeded sampler's own indices, handed to the explicit sampler, give the same events and labels: the two kernels differ in
+    where an index comes from and in nothing else.  Windows of 1, 2 and 31 pixels on a 7x5 sensor; one pixel (and N = 1) makes the
+    time row 0/0, so the events are compared as bit patterns -- torch.equal and more: a NaN has to be the same NaN."""
+    r = np.random.RandomState(90 + N)
+    wins = []
+    for M in (1, 2, 31):
+        pix = np.repeat(r.permutation(35)[:M], 2)
+        t = 5.0 + np.cumsum(r.randint(1, 4, 2 * M)).astype(np.float64)
+        wins.append(np.stack([pix % 7 + 0.25, pix // 7 + 0.5, t, r.randint(0, 2, 2 * M).astype(np.float64)], 1))
+    bld = builder(dev, n_events=N, width=7, height=5, cap=32)
+    table, counts = bld.accumulate(wins)
+    assert counts.tolist() == [1, 2, 31]
+    labels = torch.from_numpy(r.randint(0, 9, (3, bld.cap)).astype(np.int32)).to(dev)
+    ids = torch.tensor([4, 0, 2 ** 31 - 2], dtype=torch.int32, device=dev)
+    events, lab, idx = bld.sample_seeded(table, counts, 2 ** 63 + 17, ids, labels=labels, return_idx=True)
+    assert tuple(idx.shape) == (3, N) and all(0 <= int(idx[b].min()) and int(idx[b].max()) < M for b, M in enumerate((1, 2, 31)))
+    again, lab_again = bld.sample(table, counts, idx.cpu().numpy(), labels)
+    assert tuple(events.shape) == (3, 5, N) and torch.equal(again.view(torch.int32), events.view(torch.int32))
+    assert lab.dtype == torch.int64 and torch.equal(lab_again, lab)
+    if N > 1:
+        assert torch.isfinite(events[2]).all() and torch.isnan(events[0, 2]).all()
+
+
 # ---------------------------------------------------------------------------------------------------- time sort (Ev2Hands-S)
 def s_rows(n_pixels, seed, per_pixel=1, equal_times=False):
     """[n_pixels * per_pixel, 6] rows (x, y, t_ns, p, annotation, label) that hit exactly n_pixels distinct pixels"""
