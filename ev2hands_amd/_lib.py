@@ -97,7 +97,8 @@ W_EQUALIZED, W_UNEQUALIZED_OK = 1, 2
 # and for the seeded-draw / recording-evaluation exports (ev2h_event_window_sample_seeded, ev2h_fps_init_seeded, ev2h_joint_metrics_frames,
 # ev2h_eval_accumulate), and for ev2h_events_undistort, and for the synthetic-set evaluation exports (ev2h_event_window_build_s_ranges,
 # ev2h_joint_metrics_f32_frames, ev2h_segmentation_score, ev2h_eval_s_accumulate), and for the loss exports (ev2h_loss_terms,
-# ev2h_loss_accumulate), and for the augmented training item (ev2h_event_window_build_s_ranges_aug).
+# ev2h_loss_accumulate), and for the augmented training item (ev2h_event_window_build_s_ranges_aug), and for the fine-tuning item
+# (ev2h_event_window_build_ranges_flip, ev2h_finetune_resolve, ev2h_finetune_targets).
 ABI_VERSION = 8     # 8: EV2H_PREC_F16 (one fp16 plane with f16x2's range machinery); 3: F16X2 range records; 4: ev2h_fp_mlp, ev2h_weights.fp1m; 5: window strides of the outputs; 6: ev2h_pack_weights, ev2h_weights.flags; 7: ev2h_sa_desc.xyz_out
 
 PREC = {"f32": 0, "bf16": 1, "f16x2": 2, "bf16x3": 3, "f16": 4}
@@ -131,6 +132,7 @@ EXPORTS = [
     "ev2h_event_window_build_s_ranges", "ev2h_joint_metrics_f32_frames", "ev2h_segmentation_score", "ev2h_eval_s_accumulate",
     "ev2h_loss_terms", "ev2h_loss_accumulate",
     "ev2h_event_window_build_s_ranges_aug",
+    "ev2h_event_window_build_ranges_flip", "ev2h_finetune_resolve", "ev2h_finetune_targets",
 ]
 
 _lib = None
@@ -213,6 +215,9 @@ def lib() -> C.CDLL:
     L.ev2h_event_stream_walk.argtypes = [vp, vp, ci, ci, vp, ci, vp, vp, vp, vp]
     L.ev2h_events_undistort.argtypes = [vp, ci, ci, C.POINTER(C.c_double), C.POINTER(C.c_double), ci, ci, ci, vp, vp]
     L.ev2h_event_window_build_ranges.argtypes = [vp, ci, ci, vp, vp, ci, ci, ci, ci, ci, vp, vp, vp, vp, vp]
+    L.ev2h_event_window_build_ranges_flip.argtypes = [vp, ci, ci, vp, vp, ci, ci, ci, ci, ci, C.c_uint64, vp, vp, vp, vp, vp, vp, vp]
+    L.ev2h_finetune_resolve.argtypes = [vp, ci, ci, vp, vp, ci, vp, vp, ci, C.c_uint64, ci, ci, ci] + [vp] * 9 + [vp]
+    L.ev2h_finetune_targets.argtypes = [vp, ci, vp, vp, ci, vp, vp, vp, vp, vp, vp, ci, vp, ci, ci] + [vp] * 8 + [vp]
     L.ev2h_event_window_sample_seeded.argtypes = [vp, vp, ci, C.c_uint64, vp, ci, ci, ci, ci, vp, vp, vp, vp, vp, vp]
     L.ev2h_fps_init_seeded.argtypes = [C.c_uint64, vp, ci, ci, ci, vp, vp]
     L.ev2h_joint_metrics_frames.argtypes = [vp, vp, vp, ci, vp, ci, ci, C.c_double, vp, vp, vp, vp, vp, vp]

@@ -17,6 +17,7 @@
 // the seeded sampler refuses a window with M outside [1, cap].
 #include "common.hpp"
 #include "ev2hands_hip.h"
+#include "lds_sort.hpp"
 #include "random.hpp"
 
 namespace {
@@ -27,36 +28,9 @@ constexpr int EVW_MAX_EVENTS = 32768;
 // 32766 or 32767 would pack to exactly those two.  So the last pixel a sensor may have is 131070.
 constexpr long long EVW_MAX_PIXELS = (1 << 17) - 1;
 
-__host__ __device__ __forceinline__ int pow2_at_least(int v) {
-    int n = 1;
-    while (n < v) n <<= 1;
-    return n;
-}
-
-// The one bitonic network: ascending sort of n (a power of two) LDS positions by the whole workgroup.  load(i) gives the entry at
-// position i (anything with operator>), store(i, e) puts one there.  Both entries of a pair are read whole before they are compared:
-// a "greater" and a "swap" on positions made the compiler read the pair sort's source indices twice, which the clock showed.  Equal
-// entries only ever carry equal payloads here (padding, dropped events, equal frame values, or keys made unique by an index), so
-// the result does not depend on how ties fall.
-template <class Load, class Store>
-__device__ __forceinline__ void bitonic_sort_lds(int n, int tid, Load load, Store store) {
-    for (int k2 = 2; k2 <= n; k2 <<= 1) {
-        for (int j = k2 >> 1; j > 0; j >>= 1) {
-            for (int i = tid; i < n; i += EVW_THREADS) {
-                const int ixj = i ^ j;
-                if (ixj > i) {
-                    const auto a = load(i), c = load(ixj);
-                    if ((a > c) == ((i & k2) == 0)) { store(i, c); store(ixj, a); }
-                }
-            }
-            __syncthreads();
-        }
-    }
-}
+// the bitonic network of lds_sort.hpp by this file's workgroup
 template <class Key>
-__device__ __forceinline__ void bitonic_sort_keys(Key* keys, int n, int tid) {
-    bitonic_sort_lds(n, tid, [=](int i) { return keys[i]; }, [=](int i, Key k) { keys[i] = k; });
-}
+__device__ __forceinline__ void bitonic_sort_keys(Key* keys, int n, int tid) { ::bitonic_sort_keys<EVW_THREADS>(keys, n, tid); }
 
 // order-preserving maps of IEEE floats / doubles to unsigned, and back
 __device__ __forceinline__ unsigned time_key(float t) {
@@ -76,14 +50,37 @@ __device__ __forceinline__ int window_rows_s(int s, int n_events, int n_rows) {
     return (s >= 0 && s < n_rows) ? min(n_events, n_rows - s) : 0;
 }
 
+// The polarity the table counts for row e of a window (its offset from the window's first row) whose stored polarity is p.
+// PlainPolarity: the stored one, every builder's rule.  FlipPolarity (ev2h_event_window_build_ranges_flip): the augmentation
+// dataset/ev2hands_r.py:14-18 intends, |1 - p| in float64 on the rows a seeded mask picks (random.hpp, stream 4), in windows whose
+// coin is up.  `window(b)` gives window b's functor.
+struct PlainPolarity {
+    __device__ __forceinline__ PlainPolarity window(int) const { return *this; }
+    __device__ __forceinline__ double operator()(int, double p) const { return p; }
+};
+struct FlipPolarity {
+    unsigned long long seed;
+    const int32_t* window_ids;
+    const int32_t* coin;
+    struct Window {
+        unsigned long long seed;
+        uint32_t wid;
+        bool on;
+        __device__ __forceinline__ double operator()(int e, double p) const {
+            return (on && ev2h_random::flip_bit(seed, wid, (uint32_t)e)) ? fabs(__dsub_rn(1.0, p)) : p;
+        }
+    };
+    __device__ __forceinline__ Window window(int b) const { return Window{seed, (uint32_t)window_ids[b], coin[b] != 0}; }
+};
+
 // One window by one workgroup: `ev` = its first row, E = its rows.  STREAM_US = false: column 2 holds the times the reference's
 // arrays hold (the caller cut and scaled them); true: rows of a resident recording, column 2 in microseconds -- the kernel applies
 // evaluation_stream.py:102,187 itself, t * 1e-3 rounded, then minus the rounded product of the window's first row (two roundings
 // before the subtraction, never a fused multiply-subtract).  Returns whether the table was built (uniform over the workgroup).
-template <bool STREAM_US>
+template <bool STREAM_US, class Polarity = PlainPolarity>
 __device__ __forceinline__ bool event_window_build_body(const double* __restrict__ ev, int E, int b, int width, int height, int cap, int raw_time,
                                                         int ev_stride, int32_t* __restrict__ uniq_count, float* __restrict__ uniq,
-                                                        unsigned* keys, int* s_part) {
+                                                        unsigned* keys, int* s_part, Polarity polarity = Polarity{}) {
     const int tid = threadIdx.x;
     if (E <= 0 || E > EVW_MAX_EVENTS) {
         if (tid == 0) uniq_count[b] = (E <= 0) ? 0 : -1;
@@ -138,7 +135,7 @@ __device__ __forceinline__ bool event_window_build_body(const double* __restrict
             // np.add.at(float32 grid, float64 t): each step adds in float64 and rounds the running sum to float32
             const double te = ev[(size_t)e * ev_stride + 2];
             tsum = (float)((double)tsum + (STREAM_US ? __dsub_rn(__dmul_rn(te, 1e-3), t0) : te - t0));
-            pos += (ev[(size_t)e * ev_stride + 3] == 1.0) ? 1 : 0;
+            pos += (polarity(e, ev[(size_t)e * ev_stride + 3]) == 1.0) ? 1 : 0;
             ++cnt;
         }
         if (u < cap) {
@@ -168,11 +165,14 @@ __global__ __launch_bounds__(EVW_THREADS) void event_window_build_kernel(const d
 // The same table for rows starts[b] .. ends[b]-1 of a resident recording (ev2h_event_stream_walk's ranges), plus the window's frame
 // bookkeeping (evaluation_stream.py:183-184,221-222): the frame column is sorted in the same LDS, frame_index = the value of the
 // longest run (the first, i.e. smallest, among equally long ones: values[np.argmax(counts)] of np.unique), first_frame = the smallest.
+// PolaritySource = PlainPolarity is ev2h_event_window_build_ranges' kernel, FlipPolarity ev2h_event_window_build_ranges_flip's.
+template <class PolaritySource>
 __global__ __launch_bounds__(EVW_THREADS) void event_window_build_ranges_kernel(const double* __restrict__ events, int ev_stride, int n_rows,
                                                                                 const int32_t* __restrict__ starts, const int32_t* __restrict__ ends,
                                                                                 int width, int height, int cap, int frame_col,
                                                                                 int32_t* __restrict__ uniq_count, float* __restrict__ uniq,
-                                                                                int32_t* __restrict__ frame_index, int32_t* __restrict__ first_frame) {
+                                                                                int32_t* __restrict__ frame_index, int32_t* __restrict__ first_frame,
+                                                                                PolaritySource polarity) {
     extern __shared__ __attribute__((aligned(16))) char smem_raw[];
     unsigned* keys = reinterpret_cast<unsigned*>(smem_raw);
     __shared__ int s_part[EVW_THREADS];
@@ -181,7 +181,7 @@ __global__ __launch_bounds__(EVW_THREADS) void event_window_build_ranges_kernel(
     const int s = starts[b], e = ends[b];
     const int E = (s >= 0 && e > s && e <= n_rows) ? e - s : 0;       // a range outside the recording is an empty window
     const double* ev = events + (size_t)(E ? s : 0) * ev_stride;
-    const bool built = event_window_build_body<true>(ev, E, b, width, height, cap, 0, ev_stride, uniq_count, uniq, keys, s_part);
+    const bool built = event_window_build_body<true>(ev, E, b, width, height, cap, 0, ev_stride, uniq_count, uniq, keys, s_part, polarity.window(b));
     if (!built || frame_col < 0) {
         if (tid == 0) frame_index[b] = first_frame[b] = -1;           // evaluation_stream.py:95-98: no fifth column
         return;
@@ -343,7 +343,7 @@ __global__ __launch_bounds__(EVW_THREADS) void event_window_augment_timesort_ker
         skeys[i] = (unsigned)i;
     }
     __syncthreads();
-    bitonic_sort_lds(n, tid, [=](int i) { return TimeSource{tkeys[i], skeys[i]}; }, [=](int i, TimeSource e) { tkeys[i] = e.t; skeys[i] = e.s; });
+    bitonic_sort_lds<EVW_THREADS>(n, tid, [=](int i) { return TimeSource{tkeys[i], skeys[i]}; }, [=](int i, TimeSource e) { tkeys[i] = e.t; skeys[i] = e.s; });
     const double tfirst = time_of_key(tkeys[0]);
     float* tout = uniq_out + (size_t)b * cap * 8;
     for (int j = tid; j < T; j += EVW_THREADS) {
@@ -481,6 +481,19 @@ int build_s_ranges(const double* events, int ev_stride, int n_rows, const int32_
     return EV2H_OK;
 }
 
+// both ev2h_event_window_build_ranges*: the checks and the launch of the kernel with the given polarity source
+template <class PolaritySource>
+int build_ranges(const double* events, int ev_stride, int n_rows, const int32_t* starts, const int32_t* ends, int B, int width, int height, int cap,
+                 int frame_col, int32_t* uniq_count, float* uniq, int32_t* frame_index, int32_t* first_frame, PolaritySource polarity, ev2h_stream_t stream) {
+    if (const int rc = check_build_args(events, ev_stride, B, width, height, cap, uniq_count, uniq)) return rc;
+    EV2H_CHECK_ARG(starts && ends && frame_index && first_frame && n_rows > 0 && frame_col < ev_stride);
+    if (const int rc = raise_dynamic_lds<event_window_build_ranges_kernel<PolaritySource>>(EVW_MAX_EVENTS * 4)) return rc;
+    event_window_build_ranges_kernel<PolaritySource><<<B, EVW_THREADS, EVW_MAX_EVENTS * 4, (hipStream_t)stream>>>(
+        events, ev_stride, n_rows, starts, ends, width, height, cap, frame_col, uniq_count, uniq, frame_index, first_frame, polarity);
+    EV2H_CHECK_LAUNCH();
+    return EV2H_OK;
+}
+
 }  // namespace
 
 extern "C" int ev2h_event_window_build(const double* events, int ev_stride, const int32_t* offsets, int B, int width, int height, int cap,
@@ -496,13 +509,17 @@ extern "C" int ev2h_event_window_build(const double* events, int ev_stride, cons
 extern "C" int ev2h_event_window_build_ranges(const double* events, int ev_stride, int n_rows, const int32_t* starts, const int32_t* ends, int B,
                                               int width, int height, int cap, int frame_col, int32_t* uniq_count, float* uniq,
                                               int32_t* frame_index, int32_t* first_frame, ev2h_stream_t stream) {
-    if (const int rc = check_build_args(events, ev_stride, B, width, height, cap, uniq_count, uniq)) return rc;
-    EV2H_CHECK_ARG(starts && ends && frame_index && first_frame && n_rows > 0 && frame_col < ev_stride);
-    if (const int rc = raise_dynamic_lds<event_window_build_ranges_kernel>(EVW_MAX_EVENTS * 4)) return rc;
-    event_window_build_ranges_kernel<<<B, EVW_THREADS, EVW_MAX_EVENTS * 4, (hipStream_t)stream>>>(events, ev_stride, n_rows, starts, ends, width, height, cap,
-                                                                                                  frame_col, uniq_count, uniq, frame_index, first_frame);
-    EV2H_CHECK_LAUNCH();
-    return EV2H_OK;
+    return build_ranges(events, ev_stride, n_rows, starts, ends, B, width, height, cap, frame_col, uniq_count, uniq, frame_index, first_frame,
+                        PlainPolarity{}, stream);
+}
+
+extern "C" int ev2h_event_window_build_ranges_flip(const double* events, int ev_stride, int n_rows, const int32_t* starts, const int32_t* ends, int B,
+                                                   int width, int height, int cap, int frame_col, uint64_t seed, const int32_t* window_ids,
+                                                   const int32_t* coin, int32_t* uniq_count, float* uniq, int32_t* frame_index,
+                                                   int32_t* first_frame, ev2h_stream_t stream) {
+    EV2H_CHECK_ARG(window_ids && coin);
+    return build_ranges(events, ev_stride, n_rows, starts, ends, B, width, height, cap, frame_col, uniq_count, uniq, frame_index, first_frame,
+                        FlipPolarity{(unsigned long long)seed, window_ids, coin}, stream);
 }
 
 extern "C" int ev2h_event_window_timesort(const float* uniq_in, const int32_t* uniq_count, int cap, const double* events, int ev_stride,

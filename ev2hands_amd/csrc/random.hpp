@@ -13,6 +13,11 @@
 //       mean time the noise time starts from), ps = w3 & 1, a = (w3 >> 8) & 7, b = (w3 >> 16) & 7; n_pos = a + ps, n_neg = b + !ps
 //     noise row j, block 2 + 2j: u = ((w0 >> 5) * 2^26 + (w1 >> 6)) * 2^-53, a double in [0, 1) with 53 random bits;
 //       t = (double)t_avg[src] + u * 1e3, the product rounded before the sum
+//   stream 3, the Ev2Hands-R fine-tuning item (finetune.hip: finetune_resolve_kernel): block a belongs to attempt a = 0, 1, ... of a window;
+//     the window length is 1 + (w0 >> 31) ms, the coin is up iff w1 >= 2^31, and if the attempt at global index i is rejected the
+//     next index is bounded(w2, i - (min_events - 1)), the reference's inclusive randint(0, i - 2048) at min_events = 2048
+//   stream 4, the polarity flips of an augmented fine-tuning window (events.hip: FlipPolarity): row e of the window (e < 32768, counted
+//     from its first row) is flipped iff bit e & 31 of word (e >> 5) & 3 of block e >> 7 is set
 //   a 32-bit word u becomes an index below M by multiply-shift, (u * M) >> 32 in 64 bits.  There is NO rejection step, so the
 //   indices are not exactly uniform: some values are hit by ceil(2^32 / M) words and the others by floor(2^32 / M), a relative
 //   bias of at most M / 2^32 -- below 7.7e-6 for M <= 32768 (the largest table a window can have).
@@ -25,7 +30,7 @@ namespace ev2h_random {
 
 constexpr uint32_t PHILOX_M0 = 0xD2511F53u, PHILOX_M1 = 0xCD9E8D57u;        // round multipliers
 constexpr uint32_t PHILOX_W0 = 0x9E3779B9u, PHILOX_W1 = 0xBB67AE85u;        // key increments (Weyl sequence)
-constexpr uint32_t STREAM_SAMPLE = 0, STREAM_FPS = 1, STREAM_AUGMENT = 2;
+constexpr uint32_t STREAM_SAMPLE = 0, STREAM_FPS = 1, STREAM_AUGMENT = 2, STREAM_FINETUNE = 3, STREAM_FLIP = 4;
 
 struct u32x4 { uint32_t v[4]; };
 
@@ -56,12 +61,18 @@ __device__ __forceinline__ double unit_double(uint32_t w0, uint32_t w1) {
     return (double)(((uint64_t)(w0 >> 5) << 26) | (uint64_t)(w1 >> 6)) * 0x1p-53;
 }
 
+// word w (0..3) of a block by selects, not an indexed (scratch) read
+__device__ __forceinline__ uint32_t block_word(const u32x4& b, uint32_t w) { return w == 0 ? b.v[0] : w == 1 ? b.v[1] : w == 2 ? b.v[2] : b.v[3]; }
+
+// whether row e of window window_id is flipped (stream 4)
+__device__ __forceinline__ bool flip_bit(uint64_t seed, uint32_t window_id, uint32_t e) {
+    return (block_word(window_block(seed, window_id, STREAM_FLIP, e >> 7), (e >> 5) & 3u) >> (e & 31u)) & 1u;
+}
+
 // resampling index n of a window with M unique pixels
 __device__ __forceinline__ int sample_index(uint64_t seed, uint32_t window_id, uint32_t n, uint32_t M) {
     const u32x4 b = window_block(seed, window_id, STREAM_SAMPLE, n >> 2);
-    const uint32_t w = n & 3u;
-    const uint32_t u = w == 0 ? b.v[0] : w == 1 ? b.v[1] : w == 2 ? b.v[2] : b.v[3];      // selects, not an indexed (scratch) read
-    return (int)bounded(u, M);
+    return (int)bounded(block_word(b, n & 3u), M);
 }
 
 }  // namespace ev2h_random

@@ -2,52 +2,19 @@
 // Reference: /root/reference/src/Ev2Hands/dataset/evaluation_stream.py:53-146 (EvalutaionStream.get_event, get_events_by_time,
 // next_event_time) and :177-184 (ERPCParser.__getitem__ calls them in this order), which touch one event per Python step.
 //
-// Rows are (x, y, t_us, polarity[, frame]) float64 in stream order.  t_ms(i) = t_us[i] * 1e-3 rounded once (:102) and
-// far(s, j, w) = |t_ms(j) - t_ms(s)| > w in float64 (:74-76, :138-140); every product and difference below is an explicitly
-// rounded operation, a fused t * 1e-3 - c would be another number.  With non-decreasing timestamps far() is monotone in j, so
-// both of the reference's scans are searches: a gallop from s (neighbouring threads then read neighbouring rows) closed by a
-// bisection.
+// Rows are (x, y, t_us, polarity[, frame]) float64 in stream order; stream_search.hpp holds the two searches (and their explicitly
+// rounded arithmetic) that the reference's scans become for non-decreasing timestamps.
 //   end(s)  = the first j > s with j - s >= min_events and far(s, j, window_ms) (:140), -1 if the recording ends first (:88-91)
 //   next(s) = s + o + 1 for the first ODD offset o with far(s, s + o, overlap_ms): get_event (:100) and the loop (:79) both
 //             increment n_events, so next_event_time only looks at every other row; -1 if such a read runs past the recording,
 //             and then ERPCParser.__getitem__ never returns the window it had just cut (:180-181).
 #include "common.hpp"
 #include "ev2hands_hip.h"
+#include "stream_search.hpp"
 
 namespace {
 
 constexpr unsigned EVS_NO_ROW = 0xffffffffu;
-
-__device__ __forceinline__ double stream_t_ms(const double* __restrict__ ev, int stride, int i) {
-    return __dmul_rn(ev[(size_t)i * stride + 2], 1e-3);
-}
-
-// the first j in (s, E) with |t_ms(j) - t_ms(s)| > w, E if there is none
-__device__ __forceinline__ int stream_first_far(const double* __restrict__ ev, int stride, int E, int s, double w) {
-    const double ts = stream_t_ms(ev, stride, s);
-    int lo = s, hi = E;                                            // row lo is not far, row hi is (or is E)
-    for (long long step = 1;; step <<= 1) {
-        const long long p = (long long)s + step;
-        if (p >= E) break;
-        if (fabs(__dsub_rn(stream_t_ms(ev, stride, (int)p), ts)) > w) { hi = (int)p; break; }
-        lo = (int)p;
-    }
-    while (hi - lo > 1) {
-        const int mid = lo + ((hi - lo) >> 1);
-        if (fabs(__dsub_rn(stream_t_ms(ev, stride, mid), ts)) > w) hi = mid; else lo = mid;
-    }
-    return hi;
-}
-
-__device__ __forceinline__ int stream_window_end(const double* __restrict__ ev, int stride, int E, int s, double window_ms, int min_events) {
-    const long long e = max((long long)stream_first_far(ev, stride, E, s, window_ms), (long long)s + min_events);
-    return e < E ? (int)e : -1;
-}
-
-__device__ __forceinline__ int stream_next_start(const double* __restrict__ ev, int stride, int E, int s, double overlap_ms) {
-    const int o = (stream_first_far(ev, stride, E, s, overlap_ms) - s) | 1;        // the first odd offset at or behind it
-    return (long long)s + o < E ? s + o + 1 : -1;
-}
 
 __global__ __launch_bounds__(256) void event_stream_links_kernel(const double* __restrict__ ev, int stride, int E, double window_ms, double overlap_ms,
                                                                  int min_events, int32_t* __restrict__ end, int32_t* __restrict__ next,

@@ -44,27 +44,38 @@ class EventWindowBuilder:
         self._last = (ev, off)
         return table, counts
 
-    def accumulate_ranges(self, stream, starts, ends, out=None):
+    def accumulate_ranges(self, stream, starts, ends, out=None, flip=None):
         """`accumulate` for the windows rows starts[b] .. ends[b]-1 of a resident recording (ev2hands_amd.stream.EventStream; starts /
         ends device int32 [B], e.g. slices of EventStream.cut()'s): nothing is copied, the kernel reads the recording in place and
         applies evaluation_stream.py:102,187 to the timestamps itself.  Returns (table, counts, frame_index [B] i32, first_frame [B]
         i32): table and counts bit for bit those of `accumulate` on the host-cut windows, frame_index the window's most frequent
         frame (:221-222), first_frame its smallest (:183-184), both -1 for a recording without a frame column.  `out`: such a
-        4-tuple to write into."""
+        4-tuple to write into.
+        flip=(seed, window_ids, coin), window_ids and coin contiguous device int32 [B]: the polarity augmentation that
+        dataset/ev2hands_r.py:14-18 intends (ev2h_event_window_build_ranges_flip): where coin[b] != 0, the rows of window b that a
+        seeded mask picks (csrc/random.hpp, stream 4) count with polarity |1 - p|.  None: the unchanged call."""
         if self.raw_time:
             raise RuntimeError("accumulate_ranges builds evaluation windows (timestamps minus the window's first)")
         B = int(starts.shape[0])
-        for t, name in ((starts, "starts"), (ends, "ends")):
+        contract = [(starts, "starts"), (ends, "ends")]
+        if flip is not None:
+            seed, window_ids, coin = flip
+            if not 0 <= int(seed) < 2 ** 64:
+                raise ValueError("seed must be an unsigned 64-bit integer")
+            contract += [(window_ids, "window_ids"), (coin, "coin")]
+        for t, name in contract:
             _dev_tensor(t, name, torch.int32, (B,), stream.events.device)
         if out is None:
             out = (torch.empty(B, self.cap, 8, device=self.device, dtype=torch.float32), torch.empty(B, device=self.device, dtype=torch.int32),
                    torch.empty(B, device=self.device, dtype=torch.int32), torch.empty(B, device=self.device, dtype=torch.int32))
         table, counts, frame_index, first_frame = out
-        if B:
-            _lib.check(_lib.lib().ev2h_event_window_build_ranges(stream.events.data_ptr(), stream.stride, stream.n_rows, starts.data_ptr(),
-                                                                 ends.data_ptr(), B, self.w, self.h, self.cap, stream.frame_col, counts.data_ptr(),
-                                                                 table.data_ptr(), frame_index.data_ptr(), first_frame.data_ptr(),
-                                                                 _lib.stream_handle()), "ev2h_event_window_build_ranges")
+        head = (stream.events.data_ptr(), stream.stride, stream.n_rows, starts.data_ptr(), ends.data_ptr(), B, self.w, self.h, self.cap, stream.frame_col)
+        tail = (counts.data_ptr(), table.data_ptr(), frame_index.data_ptr(), first_frame.data_ptr(), _lib.stream_handle())
+        if B and flip is not None:
+            _lib.check(_lib.lib().ev2h_event_window_build_ranges_flip(*head, int(seed), window_ids.data_ptr(), coin.data_ptr(), *tail),
+                       "ev2h_event_window_build_ranges_flip")
+        elif B:
+            _lib.check(_lib.lib().ev2h_event_window_build_ranges(*head, *tail), "ev2h_event_window_build_ranges")
         return table, counts, frame_index, first_frame
 
     def sample(self, table, counts, sample_idx=None, labels=None):

@@ -524,6 +524,70 @@ int ev2h_event_window_build_ranges(const double* events, int ev_stride, int n_ro
                                    int width, int height, int cap, int frame_col, int32_t* uniq_count, float* uniq,
                                    int32_t* frame_index, int32_t* first_frame, ev2h_stream_t stream);
 
+/* ---- recordings -> fine-tuning items (dataset/ev2hands_r.py:91-184, dataset/evaluation_stream.py:84-162, src/camera.py:56-70) ---- */
+/* ev2h_event_window_build_ranges with the augmentation that dataset/ev2hands_r.py:14-18 INTENDS (upstream assigns into a copy and
+ * flips nothing, so the reference-faithful item never calls this): in a window with coin[b] != 0, row e of the window (its offset
+ * from row starts[b], e < 32768) has its polarity p replaced by |1 - p|, one rounded float64 subtraction, BEFORE the == 1 test, iff
+ * bit e & 31 of word (e >> 5) & 3 of Philox4x32-10 block e >> 7 under counter (block, window_ids[b], 4, 0) is set (csrc/random.hpp,
+ * stream 4).  Nothing else differs: a window whose coin is 0 gets ev2h_event_window_build_ranges' table bit for bit, and so does
+ * the table of a window whose polarity column was flipped on the host by the same mask; frame_index and first_frame do not depend
+ * on the polarity.  window_ids, coin: device int32 [B]. */
+int ev2h_event_window_build_ranges_flip(const double* events, int ev_stride, int n_rows, const int32_t* starts, const int32_t* ends, int B,
+                                        int width, int height, int cap, int frame_col, uint64_t seed, const int32_t* window_ids,
+                                        const int32_t* coin, int32_t* uniq_count, float* uniq, int32_t* frame_index, int32_t* first_frame,
+                                        ev2h_stream_t stream);
+/* A recording SET is R recordings back to back in one device table of n_rows (< 2^31) float64 rows of ev_stride (>= 5) columns (x, y,
+ * t_us, polarity, frame index), each with non-decreasing timestamps: recording r owns rows row_offsets[r] .. row_offsets[r+1]-1
+ * (device int32 [R+1], row_offsets[0] = 0, row_offsets[R] = n_rows) and F_r = joint_offsets[r+1] - joint_offsets[r] rows of the
+ * joints table.  A global sample index i is row i of the table (Ev2HandRDataset.sample_indices, :68-81).
+ * ev2h_finetune_resolve: which window item b is, one workgroup of 256 per item.  Attempt a = 0, 1, ... at index i (i = indices[b] for
+ * a = 0) draws Philox4x32-10 block a under counter (a, window_ids[b], 3, 0) (csrc/random.hpp, stream 3):
+ *   length    1 + (w0 >> 31) ms                                          (np.random.randint(1, 3), :99)
+ *   coin      up iff w1 >= 2^31; coin[b] = that AND augment != 0          (random.random() > 0.5, :104; drawn whatever it is used for)
+ * and is ACCEPTED iff all of
+ *   0 <= i < n_rows, with r = the recording that owns row i and s = i - row_offsets[r];
+ *   e = the end of ev2h_event_stream_ends for start s, that length and min_events IN RECORDING r ALONE -- the search stops at r's
+ *       last row and never reads a neighbour's -- is not -1 (StopIteration, :100);
+ *   every row of s .. e-1 has an integer-valued frame f with 0 <= f < F_r (a block-wide test of all e - s rows).
+ * The last rule is this project's own, conservative form of :139-144: upstream looks up only the frame its sampling elects, which is
+ * known after the table is built, and redraws if THAT lookup fails.  A window accepted here has every frame in range, so upstream
+ * accepts it too; upstream may also keep a window this rule rejects.
+ * A rejected attempt at i >= min_events is followed by attempt a + 1 at i' = (w2 * (i - (min_events - 1))) >> 32 -- upstream's inclusive
+ * random.randint(0, index - 2048) on the GLOBAL index (:101,143), so the redraw may land in an earlier recording.  The item FAILS when
+ * a rejected attempt has i < min_events (upstream raises there) or when attempt max_redraws is rejected (at most max_redraws redraws).
+ * Outputs (device, [B]): recording = r, start = s, end = e (rows local to r), first_row / last_row = row_offsets[r] + s / + e (the
+ * ranges ev2h_event_window_build_ranges takes with the whole table as its recording), window_ms (float64), coin, attempts = the
+ * number of attempts made.  A failed item: -1 in the five row outputs (an empty window for the builder), window_ms 0, coin 0, and
+ * window_ids[b] lowered into *status (device int32 the caller set to INT32_MAX; atomicMin).  A window of more than 32768 rows is
+ * accepted here and refused by the builder (count -1).  One launch, no host synchronisation, allocates nothing, capturable. */
+int ev2h_finetune_resolve(const double* events, int ev_stride, int n_rows, const int32_t* row_offsets, const int32_t* joint_offsets, int R,
+                          const int32_t* indices, const int32_t* window_ids, int B, uint64_t seed, int min_events, int max_redraws,
+                          int augment, int32_t* recording, int32_t* start, int32_t* end, int32_t* first_row, int32_t* last_row,
+                          double* window_ms, int32_t* coin, int32_t* attempts, int32_t* status, ev2h_stream_t stream);
+/* The item's frame, joints and projection (:132-144,172-180), one workgroup of 256 per item.  joints: device float64 [sum F_r][2][21][3]
+ * in metres; cameras: device float64 [R][9], row-major K; recording / start / end as ev2h_finetune_resolve writes them;
+ * uniq_count [B] and cap the built table's; sample_idx [B][N] int32 the resampling indices (1 <= N <= 8192).
+ *   frame   window_frame = NULL: the most frequent of the N values frame(row_offsets[r] + start[b] + idx[n]), the SMALLEST on ties --
+ *           :134 indexes the per-ROW frame list with the indices drawn over the M unique PIXELS, and :136-137 (np.unique ascends,
+ *           sorted() is stable) keeps the first of equally frequent values.  idx outside [0, min(M, cap, end - start)) counts as 0,
+ *           the sampler's rule.  Exact for arbitrary int32 values: a sort in LDS padded to a power of two, then run lengths.
+ *           window_frame != NULL (device int32 [B], e.g. ev2h_event_window_build_ranges' frame_index): that value instead.
+ *   j3d     [B][2][21][3] float32 = (float) joints[joint_offsets[r] + frame]                              (:173,177)
+ *   j2d     [B][2][21][2] float32: mm = j * 1000; u = (K00*mm.x + K01*mm.y) + K02*mm.z, v and w likewise with rows 1 and 2 of K,
+ *           every product and sum one rounded float64 operation, none contracted; j2d = ((float)(u / w), (float)(v / w))
+ *           (camera.py:64-68 on joints * 1000, evaluation_stream.py:162)
+ *   valid   [B] uint8 = 1, frame_index [B] = frame.
+ * An item FAILS if recording[b] is outside [0, R), its range is not inside its recording, uniq_count[b] is outside [1, cap], or the
+ * frame is outside [0, F_r) (possible only for caller-given ranges: ev2h_finetune_resolve accepts no such window).  Then j3d, j2d and
+ * the item's events_out [5][N] (device float32 [B][5][N], the sampler's output) are zeros, valid 0, recording[b] becomes -1 and
+ * window_ids[b] is lowered into *status (atomicMin).  Nothing of `joints` is read for such an item.  One launch, no host
+ * synchronisation, allocates nothing, capturable. */
+int ev2h_finetune_targets(const double* events, int ev_stride, const int32_t* row_offsets, const int32_t* joint_offsets, int R,
+                          const double* joints, const double* cameras, int32_t* recording, const int32_t* start, const int32_t* end,
+                          const int32_t* uniq_count, int cap, const int32_t* sample_idx, int B, int N, const int32_t* window_frame,
+                          const int32_t* window_ids, int32_t* frame_index, float* events_out, float* j3d, float* j2d, uint8_t* valid,
+                          int32_t* status, ev2h_stream_t stream);
+
 /* ---- per-frame joint metrics (next row 8f-3; evaluate.py:185-234, evaluate_ev2hands_r.py:35-89) ------------------------ */
 /* j3d_left / j3d_right [B][21][3] float32 metres (the forward's outputs); j3d_gts [B][G][2][21][3] float64 metres (G ground-truth
  * candidates per frame).  For the candidate with the best rounded right-root-relative AUC (first on ties): pck [B][3][num_steps+1]
