@@ -330,6 +330,23 @@ static int forward_body(const ev2h_weights* w, const ev2h_mano_consts* const* ma
     static const int chunk_env = [] { const char* e = getenv("EV2H_FPS_CHUNKS"); return e ? atoi(e) : -1; }();
     const int chunk_max_wg = chunk_env > 1 ? chunk_env : (N <= 2048 ? 0x7fffffff : 256), chunk_min_b = chunk_env > 1 ? 1 : 8;
     const bool chunked = fork && chunk_env != 0 && B >= chunk_min_b && 3 * B <= chunk_max_wg && bf16_direct_layer1(prec, w->sa1) && w->sa1.npoint % FPS_CHUNKS == 0;
+    // From 64 windows of at most 2048 points on, the fused kernels of a quarter outlast its selections, and what stands in the way is
+    // whatever is NOT a matrix-pipe kernel on the caller's stream (256 x 2048, tools/sa1_exposed.py: 0.25 ms before the first fused
+    // launch and 0.26 ms of ball queries between the later ones).  There the side stream runs each quarter's ball query right behind
+    // its sampling and the caller's stream launches nothing but fused kernels; the sampling is a ONE-job launch (one workgroup per CU
+    // at 256 windows instead of three, on a VALU-bound kernel that everything waits for; job 0's slots of WS_FPS_STATE) -- the
+    // regressors' two samplings, which rode in the first launch, are drawn behind the last quarter, still ahead of everything that
+    // reads them (right behind quarter 0 they cost all that was won).  The queries cost the fused kernels beside them nearly what they
+    // took alone (the CUs' issue slots are shared: enc.sa1 stays at 2.6 ms from first to last launch while its idle time falls from
+    // 0.26 to 0.02 ms); what is won is the head, 0.25 -> 0.20 ms, and the caller's stream's launches: 256 x 2048 -0.8 .. -1.3 % step
+    // time on four machines, bf16 -0.8 %.
+    // Below 64 windows, and at 8192 points, the sampling is the critical path and a query between two of its chunks delays it
+    // (8 x 2048 +11 %, 32 x 2048 +5 %, 16 x 8192 +11 %, 64 x 8192 +1.2 % step time: profiles/sa1_selections_ab.txt) -- those keep the
+    // schedule above.  Same kernels on the same groups either way: bit-identical outputs.
+    const bool side_queries = chunked && B >= 64 && N <= 2048;
+    int32_t* gi1[3] = {ws.i(WS_GIDX1_0), ws.i(WS_GIDX1_1), ws.i(WS_GIDX1_2)};
+    double rad1[3]; int ns1[3];
+    for (int i = 0; i < 3; ++i) { rad1[i] = w->sa1.br[i].radius; ns1[i] = w->sa1.br[i].K; }
     {
         const int S[3] = {512, 128, 128};
         const int64_t* init[3] = {fps_init, fps_init + 2 * (size_t)B, fps_init + 3 * (size_t)B};
@@ -339,10 +356,12 @@ static int forward_body(const ev2h_weights* w, const ev2h_mano_consts* const* ma
             RUN(ev2h_fps_multi(ws.f(WS_PTS4), B, N, 3, S, init, idx, ctr, st));
         } else {
             const int q = w->sa1.npoint / FPS_CHUNKS;
-            for (int c = 0; c < FPS_CHUNKS; ++c) {          // (the regressors' 128-centroid samplings finish inside the first launch)
-                RUN(ev2h_fps_multi_chunk(ws.f(WS_PTS4), B, N, 3, S, init, idx, ctr, c * q, (c + 1) * q, ws.f(WS_FPS_STATE), sd));
+            for (int c = 0; c < FPS_CHUNKS; ++c) {          // (!side_queries: the regressors' 128-centroid samplings finish inside the first launch)
+                RUN(ev2h_fps_multi_chunk(ws.f(WS_PTS4), B, N, side_queries ? 1 : 3, S, init, idx, ctr, c * q, (c + 1) * q, ws.f(WS_FPS_STATE), sd));
+                if (side_queries) RUN(ev2h_ball_query_range(ws.f(WS_PTS4), ws.f(WS_CTR1), B, N, 512, c * q, q, 3, rad1, ns1, gi1, ws.i(WS_CNT1), sd));
                 RUN(cx.side_records(EV_SA1_QUARTER0 + c));
             }
+            if (side_queries) RUN(ev2h_fps_multi(ws.f(WS_PTS4), B, N, 2, S + 1, init + 1, idx + 1, ctr + 1, sd));
         }
     }
     // fork 1: everything that needs only COORDINATES runs on the side stream, under the MFMA-bound set-abstraction kernels of
@@ -376,20 +395,17 @@ static int forward_body(const ev2h_weights* w, const ev2h_mano_consts* const* ma
     // ---- enc.sa1 (TEHNet.py:179)
     {
         const ev2h_sa_module& m = w->sa1;
-        double rad[3]; int ns[3];
-        int32_t* gi[3] = {ws.i(WS_GIDX1_0), ws.i(WS_GIDX1_1), ws.i(WS_GIDX1_2)};
-        for (int i = 0; i < 3; ++i) { rad[i] = m.br[i].radius; ns[i] = m.br[i].K; }
         if (!chunked) {
-            RUN(ev2h_ball_query(ws.f(WS_PTS4), ws.f(WS_CTR1), B, N, 512, 3, rad, ns, gi, ws.i(WS_CNT1), st));
+            RUN(ev2h_ball_query(ws.f(WS_PTS4), ws.f(WS_CTR1), B, N, 512, 3, rad1, ns1, gi1, ws.i(WS_CNT1), st));
             RUN(cx.wait_side(EV_SA1_TABLE));
-            RUN(sa_branches(prec_sa, "sa1", m, ws.f(WS_PTS4), ws.f(WS_CTR1), gi, ws.i(WS_CNT1), B, N, ws.f(WS_P1A), ws.f(WS_L1CAT), 576, st, ws.ranges_on,
+            RUN(sa_branches(prec_sa, "sa1", m, ws.f(WS_PTS4), ws.f(WS_CTR1), gi1, ws.i(WS_CNT1), B, N, ws.f(WS_P1A), ws.f(WS_L1CAT), 576, st, ws.ranges_on,
                             ws.r(R_P1A), ws.p1scale(0), ws.r(R_L1A), ws.f(WS_FEAT8), C, ws.r(R_FEAT)));
         } else {
             const int q = m.npoint / FPS_CHUNKS;
-            for (int c = 0; c < FPS_CHUNKS; ++c) {          // quarter c: as soon as its centroids are drawn
+            for (int c = 0; c < FPS_CHUNKS; ++c) {          // quarter c: as soon as its centroids are drawn (side_queries: and their neighbours found)
                 RUN(cx.wait_side(EV_SA1_QUARTER0 + c));
-                RUN(ev2h_ball_query_range(ws.f(WS_PTS4), ws.f(WS_CTR1), B, N, 512, c * q, q, 3, rad, ns, gi, ws.i(WS_CNT1), st));
-                RUN(sa_branches(prec_sa, "sa1", m, ws.f(WS_PTS4), ws.f(WS_CTR1), gi, ws.i(WS_CNT1), B, N, ws.f(WS_P1A), ws.f(WS_L1CAT), 576, st, ws.ranges_on,
+                if (!side_queries) RUN(ev2h_ball_query_range(ws.f(WS_PTS4), ws.f(WS_CTR1), B, N, 512, c * q, q, 3, rad1, ns1, gi1, ws.i(WS_CNT1), st));
+                RUN(sa_branches(prec_sa, "sa1", m, ws.f(WS_PTS4), ws.f(WS_CTR1), gi1, ws.i(WS_CNT1), B, N, ws.f(WS_P1A), ws.f(WS_L1CAT), 576, st, ws.ranges_on,
                                 ws.r(R_P1A), ws.p1scale(0), ws.r(R_L1A), ws.f(WS_FEAT8), C, ws.r(R_FEAT), nullptr, 0, c * q, q));
             }
         }
