@@ -416,7 +416,7 @@ void sa_geometry(int C2, int* T2, int* C2P) {
 
 struct SaImages { std::vector<uint8_t> i2, i3; float u2 = 1.f, u3 = 1.f; };
 
-// Byte images of the LDS weight tiles of sa_mlp_max_bf16_kernel (SaBCfg in csrc/sa_mlp_bf16.hip).  W2 [C2][C1], W3 [C3][C2].
+// Byte images of the LDS weight tiles of sa_mlp_max_bf16_kernel and row_mlp_bf16_kernel (SaBCfg in csrc/sa_steps.hpp).  W2 [C2][C1], W3 [C3][C2].
 SaImages sa_images(const double* W2in, const double* W3in, int C1, int C2, int C3, int ns) {
     SaImages R;
     const double u2 = ns == 4 ? chain_unscale(W2in, C2, C1) : plane_unscale(W2in, (size_t)C2 * C1, ns), u3 = plane_unscale(W3in, (size_t)C3 * C2, ns);

@@ -1,4 +1,4 @@
-// Operand planes of the matrix-pipe kernels (sa_mlp_bf16.hip, gemm_bf16.hip): every fp32 operand is represented by NS
+// Operand planes of the matrix-pipe kernels (sa_mlp_bf16.hip, row_mlp_bf16.hip, gemm_bf16.hip): every fp32 operand is represented by NS
 // 16-bit planes and a product x*w by a few plane products accumulated in fp32 by v_mfma_f32_32x32x16_{bf16,f16}.
 //   NS = 1  "bf16"    one bf16 plane (round to nearest even), 1 product                      -- BASELINE.json config 3
 //   NS = 2  "f16x2"   x = h + l, two fp16 planes (h = rne(x), l = rne(x - h)): 11 + 11 mantissa bits; products

@@ -23,11 +23,15 @@
 // ds_read_b128 fragment reads are conflict free) and streamed global -> LDS with the LDS-DMA
 // (global_load_lds_dwordx4, no staging registers): two buffers and one barrier per tile step (one or two tiles) in the
 // streamed variant; the narrow MLPs keep all tiles resident in a persistent workgroup (see the kernel's comment).
+//
+// Set abstraction only.  The tile geometry (SaBCfg) and the steps of the tile walk that the row chains of ev2h_fp_mlp
+// (row_mlp_bf16.hip) take in the same way -- tile DMA, layer-2 MFMA groups, ReLU + split of H1 and H2, layer-3 MFMA loop, the
+// streamed range-record combine -- are in sa_steps.hpp, one copy each.
 #include <algorithm>
 #include <cmath>
 #include <cstdlib>
 #include <type_traits>
-#include "planes.hpp"
+#include "sa_steps.hpp"
 #include "ev2hands_hip.h"
 
 namespace {
@@ -54,14 +58,7 @@ struct SaBP {
     const float* p1_scale; const unsigned* p1_amax;   // per window: power of two the P1 table was stored with, max |stored P1|
     float w1x_norm, dmax, w2_norm, b2_max;
     unsigned* out_amax;                    // per window: atomicMax of |out|
-    // ROWS (feature propagation, ev2h_fp_mlp): a "group" is a strip of 32 consecutive points of a window; P1 is the coarse points'
-    // layer-1 table, the row of a point is the 3-NN blend of three table rows; out holds one row per point
-    const int32_t* nn_idx; const float* nn_w; int N;
-    // MODE 2 (plain row chain, e.g. the segmentation head): P1 holds the N input rows themselves (no blend, no layer-1 ReLU; F16X2:
-    // scaled here by the power of two of p1_amax); ncols = leading columns of the last tile that are written; relu_out = 0 drops
-    // the last ReLU; out_cm = optional second copy of the output, channel-major [B][ncols][N]
-    int ncols; int relu_out; float* out_cm; size_t out_cm_stride;
-    // BF16 (NS = 1), set abstraction: layer 1 runs on the matrix pipe (see L1M in the kernel).  feat != NULL: the layer-1 table is
+    // BF16 (NS = 1): layer 1 runs on the matrix pipe (see L1M in the kernel).  feat != NULL: the layer-1 table is
     // not needed at all -- the neighbour's raw feature row feat[b][idx][0..nfeat) (nfeat <= 5, row stride ldf floats) and its
     // relative xyz are contracted with [W1f | W1x | b1] directly (W1f [C1][ldw1f], b1 [C1]); feat == NULL: P1 is the table.
     const float* feat; int ldf; const float* W1f; int ldw1f; const float* b1; int nfeat;
@@ -79,15 +76,6 @@ struct SaBP {
     // One window at a time (demo.py:24-33) has 16 workgroups for 256 CUs in the 128-centroid modules: 88 -> ~25 us per launch.
     int spg;
     float* xyz_out; int xyz_ld;            // optional: the group's centroid as 8 more columns of the consumer's input rows (ev2h_sa_desc)
-    // BF16 row chains only (internal, ev2h_fp_mlp_ex): the input rows of MODE 2 / the output rows are bf16 (2 bytes per value; ldp /
-    // ldo still count VALUES) -- l0, the one N-row 256-wide tensor of the forward, is written once and read three times, and
-    // every reader of the BF16 mode rounds it to bf16 before it multiplies anyway
-    int t_bf16, out_bf16;
-    // F16 row chains only (internal, ev2h_fp_mlp_ex) [r6]: the same for the one-plane fp16 mode -- the rows are fp16 values TIMES a
-    // per-window power of two row16_scale[b] (float [B]).  The writer (out_bf16, fp1) chooses it from the rigorous bound of its own
-    // output (|W3|_1 bound(H2) + max|b3|: known before the first row is computed), stores it and records max |stored|; the reader
-    // (t_bf16, the segmentation head) takes the stored values as its operand plane as they are and the scale as its s1.
-    float* row16_scale; float w3_norm, b3_max;
 };
 
 // EV2H_SAB_TIMELINE build (EV2H_BUILD_DEFS=-DEV2H_SAB_TIMELINE python -m ev2hands_amd.build --force; tools/sa_timeline.py):
@@ -102,62 +90,6 @@ __device__ long long g_sab_timeline[256];
 // one body that chooses at run time keeps both forms' registers live (128-196-256: 249 registers instead of 224 / 214 in F16X2, a
 // 92-byte spill in BF16X3; the BF16 feature-row kernels 158 -> 124, which doubles the resident workgroups per CU) and schedules around
 // the branch.  Same-box: F16X2 step +2.3 %, BF16 +4 % (profiles/r5_ab_split_forms.txt).
-constexpr int SAB_WAVES = 8;
-constexpr int SAB_THREADS = SAB_WAVES * 64;
-
-template <int C1, int C2, int C3, int NS>
-struct SaBCfg {
-    static constexpr int NPL = plane_count(NS);                         // 16-bit planes per operand in the tile images
-    static constexpr bool F16 = planes_f16(NS);                         // fp16 planes: range records and power-of-two scaling
-    static constexpr int T2 = (C2 + 31) / 32;
-    static constexpr int REM = C2 % 32;
-    static constexpr int M_LAST = REM == 0 ? 2 : (REM <= 16 ? 1 : 2);   // live 16-wide k-blocks of the last layer-2 tile
-    static constexpr int C2P = 32 * (T2 - 1) + 16 * M_LAST;              // layer-3 contraction length (permuted order)
-    static constexpr int T3 = C3 / 32;
-    static constexpr int NC1 = C1 / 32;
-    static constexpr int RS2 = NPL * 64 + 16;                             // bytes per row of a W2 chunk tile
-    static constexpr int RS3 = NPL * C2P * 2 + 16;                        // bytes per row of a W3 tile
-    static constexpr int TB2 = T2 * 32 * RS2;
-    static constexpr int TB3 = 32 * RS3;
-    // streamed variant: a tile step moves CPT layer-2 chunk tiles or UPT layer-3 tiles at once (one DMA burst, one barrier);
-    // two per step whenever the doubled buffers still fit in LDS (measured on 128-128-256 f16x2: -16 % with 2, -11 % with 4)
-    static constexpr int SB2W = F16 ? SAB_WAVES * T2 * 32 * 4 : 0;   // F16X2: the b2 bias times each wave's window scale
-    // W1x in fp32 (12 B per channel, padded); BF16: the layer-1 A tile [C1][16 k] in bf16; F16X2: two A tiles per channel row
-    // ([wh | wh], [wl | 0]: 64 B) + the b1 bias times each wave's window scale
-    // BF16X3: three A tiles per channel row ([w0 | w0], [w1 | w1], [w2 | w0]: 96 B) + the b1 bias
-    // [r6] the L1F A rows carry a 16-byte pad (80 / 112 instead of 64 / 96 bytes): at 64 bytes per row the 32 rows a fragment read
-    // touches fall on 4 of the LDS's 256-byte bank windows eight deep -- SQ_LDS_BANK_CONFLICT 15.6 M cycles per launch in the
-    // feature-row form against 0 in the table form (profiles/r5_pmc_sq_f16x2.txt); padded like the weight tiles they are conflict free.
-    static constexpr int RSA = (NS == 3) ? 112 : 80;
-    static constexpr int W1B = (NS == 1 || NS == 4) ? C1 * 32 : F16 ? C1 * RSA + SAB_WAVES * C1 * 4 : C1 * RSA + C1 * 4;
-    // range-record combine (F16X2, end of a group): 8 x (window, max) in the streamed variants, REC_SLOTS per-window running maxima
-    // in the resident one -- see the kernel's epilogue
-    static constexpr int REC_SLOTS = 64;
-    static constexpr int REC = F16 ? REC_SLOTS * 4 : 0;
-    static constexpr int SMALL_NOREC = W1B + T2 * 32 * 4 + 16 + SB2W;      // + b2, one int for the workgroup's strip count, scaled b2
-    static constexpr int SMALL = SMALL_NOREC + REC;
-    static constexpr int tile_bytes(int cpt, int upt) { return ((cpt * TB2 > upt * TB3 ? cpt * TB2 : upt * TB3) + 1023) / 1024 * 1024; }
-    static constexpr bool fits(int n) { return NC1 % n == 0 && T3 % n == 0 && 2 * tile_bytes(n, n) + SMALL <= 158 * 1024; }
-    static constexpr int CPT = fits(2) ? 2 : 1, UPT = CPT;
-    static constexpr int TILE = tile_bytes(CPT, UPT);
-    static constexpr int LDS_BYTES = 2 * TILE + SMALL;
-    // resident variant: every tile image of the module stays in LDS for the lifetime of the (persistent) workgroup
-    static constexpr int RES_W = (NC1 * TB2 + T3 * TB3 + 1023) / 1024 * 1024;
-    static constexpr int RES_LDS_BYTES = RES_W + SMALL;
-    // streamed set abstraction: b3 and b1 behind everything else (fits() keeps 2 KiB of the 160 KiB free)
-    static constexpr int SAB_XTR = (C3 + C1) * 4;
-    static constexpr bool FITS_RESIDENT = RES_LDS_BYTES <= 160 * 1024 && C1 >= 64;   // (the 32-32-64 MLP is faster streamed: several small workgroups per CU)
-    // F16X2 with 1..4 channels left over after the last full 32-channel tile (C2 = 196: channels 192..195): the three plane
-    // products of those channels share MFMAs instead of taking three each (csrc/pack.hip builds the matching images):
-    //  * layer 2, last tile: rows 8..11 of the tile's HIGH-plane image hold the LOW plane of rows 0..3, so (A = high image,
-    //    B = xh) yields wh*xh in D rows 0..3 and wl*xh in rows 8..11 -- the separate (wl, xh) MFMA is dropped and rows 8..11 are
-    //    added to rows 0..3 in registers (same lane: D rows 8..11 are registers 4..7 of the lower half-wave);
-    //  * layer 3, last 16-slot k-block (4 live slots): the slots carry [xh | xl | xh | 0] against [wh | wh | wl | 0] -- ONE MFMA
-    //    instead of three.
-    // 24 of the 480 MFMAs of a 128-196-256 strip (5 %) disappear; the products are the same three (plus wl*xl in layer 2).
-    static constexpr bool PACK4 = (NS == 2) && REM >= 1 && REM <= 4;
-};
-
 // RES = false: weight tiles are streamed, two LDS buffers, one barrier per tile (any MLP width).  A workgroup works on an OCTET: 8
 //              consecutive groups, one per wave.  Set abstraction (MODE 0 / 3), persistent form (SaBP::pers, chosen by launch_sab when
 //              the launch has more octets than one resident wave of workgroups -- the wide MLPs at 92-152 KB of LDS run one
@@ -181,9 +113,8 @@ struct SaBCfg {
 //              persistent workgroup whose waves then walk their groups with NO barrier and no DMA in the loop -- the
 //              waves drift apart, so one wave's split (VALU) phases run under the other waves' MFMA phases, and a tile
 //              step no longer pays the DMA issue / wait / barrier that dominate when a tile holds only 6-18 MFMAs.
-// MODE = 1, 2 (streamed only): the row chains of ev2h_fp_mlp -- same tile walk, but the layer-3 tiles are written out row by row
-//              instead of maximised, and layer 1 is (1) the inverse-distance blend of three table rows (no relative xyz) or (2) the
-//              input row itself.
+// MODE = 0 / 3: the table form / the feature-row form (above).  The row chains of ev2h_fp_mlp (fp1, the segmentation head) walk the
+//              same tiles with the same steps (sa_steps.hpp) in a kernel of their own: row_mlp_bf16.hip.
 // Waves per SIMD the register allocator must leave room for: 2 (256 registers) everywhere, except F16's resident feature-row kernels
 // whose LDS footprint lets TWO workgroups share a CU -- BF16's get under 128 registers by themselves (124), F16's 64-96-128 needs 138
 // and is held to 128 (32 bytes of scratch outside the MFMA loops): kbench 0.81 -> 0.73 ms (tools/kbench.py sab, KBENCH_FEAT=1).
@@ -195,9 +126,8 @@ template <int C1, int C2, int C3, int NS, bool RES, int MODE = 0>
 __global__ __launch_bounds__(SAB_THREADS, (sab_min_waves<C1, C2, C3, NS, RES, MODE>())) void sa_mlp_max_bf16_kernel(SaBP p) {
     constexpr int WV = SAB_WAVES;
     // MODE = 3: the set abstraction with RAW FEATURE ROWS (L1M / L1F below); MODE 0 is the table form only (see above).
-    constexpr bool ROWS = MODE == 1 || MODE == 2, DIRECT = MODE == 2;
-    static_assert(!(RES && ROWS), "the row-output variants stream their tiles");
-    // BF16, set abstraction: LAYER 1 ON THE MATRIX PIPE.  D1[channel][neighbour] = A1 [32 channels][16 k] x B1 [16 k][32 neighbours]
+    static_assert(MODE == 0 || MODE == 3, "table form or feature-row form");
+    // BF16: LAYER 1 ON THE MATRIX PIPE.  D1[channel][neighbour] = A1 [32 channels][16 k] x B1 [16 k][32 neighbours]
     // (+ C = the gathered table row when the features are a table) with the k slots
     //     0..4  feature f_i (hi plane)      5..7  lo(dx, dy, dz)      8..10  hi(dx, dy, dz)      11  1.0 (x b1)      12..15  lo(f_0..f_3)
     // (hi = bf16(x), lo = bf16(x - hi): inputs keep 16 bits, the weights are bf16 like everywhere in this mode) -- one MFMA per
@@ -207,8 +137,8 @@ __global__ __launch_bounds__(SAB_THREADS, (sab_min_waves<C1, C2, C3, NS, RES, MO
     // the BF16 W2 images are stored in that order (ev2h_tile_geometry out[9] = 1), for every kernel mode.
     // F16 (NS = 4) [r6]: the same form in fp16 -- the k-slot groups carry launch-constant powers of two (SaBP::a1f / a1x / a1b), the B
     // operand the window's s1, so that D1 = s1 (W1f f + W1x d + b1) comes out of the MFMA ready for ReLU + conversion (2 VALU ops per pair).
-    constexpr bool L1M = (NS == 1 || NS == 4) && !ROWS;
-    // F16X2, set abstraction with RAW FEATURE ROWS (ev2h_sa_desc.feat): layer 1 on the matrix pipe with a power-of-two scale PER
+    constexpr bool L1M = NS == 1 || NS == 4;
+    // F16X2 with RAW FEATURE ROWS (ev2h_sa_desc.feat): layer 1 on the matrix pipe with a power-of-two scale PER
     // NEIGHBOUR.  The inputs of neighbour j -- features f0..f4 and relative xyz -- are two groups with their own weights (W1f / uf,
     // W1x / ux, planes built here) and their own input factors sigma_f = kappa_j uf, sigma_x = kappa_j ux, where
     // kappa_j = min(s_f / uf, s_x / ux) and s_g puts the group's largest input at [2^14, 2^15): both groups accumulate kappa_j times
@@ -224,20 +154,16 @@ __global__ __launch_bounds__(SAB_THREADS, (sab_min_waves<C1, C2, C3, NS, RES, MO
     // three-plane split), A = [w2 | w0] (x B1g), [w1 | w1], [w0 | w0] (x B1f): three MFMAs = the six products of Planes<3>, small terms
     // first, on top of C = b1.
     constexpr bool L1F = (NS == 2 || NS == 3) && MODE == 3;
-    // L2PIPE / H2FUSE (round 4, late): conversion work of one wave placed between its MFMA groups (see the layer-2 loop and the first
-    // layer-3 step).  Same-box step A/B (profiles/r4_ab_h2fuse_l2pipe.txt): BF16 +1.3 % with H2FUSE, +1.9 % with both; F16X2 +1.1 % with
-    // H2FUSE, and L2PIPE costs it 0.5 % (its widest instantiation then spills 24 bytes) -- so F16X2 keeps the un-pipelined layer 2.
-    constexpr bool L2PIPE = !ROWS && (NS == 1 || NS == 4) && (C1 / 32) % 2 == 0;      // (F16 [r6]: bf16's layer-1 form, bf16's pipelining)
-    constexpr bool H2FUSE = NS != 3;          // (BF16X3: the widest instantiation would spill)
-    // F16X2 [r5]: with the two layer-1 forms in separate instantiations there are registers for the second fragment set (128-196-256:
-    // 224 -> 232): dominant launch 1.622 -> 1.592 ms, step +0.65 % same-box (profiles/r5_ab_frag_pipe_f16x2.txt).  BF16X3 would spill
-    // (28 bytes in the widest instantiation).
-    constexpr bool FRAG_PIPE = (NS != 3);
+    // L2PIPE (round 4, late): conversion work of one wave placed between its MFMA groups (see the layer-2 loop; H2FUSE in sa_steps.hpp
+    // is the same idea in the first layer-3 step).  Same-box step A/B (profiles/r4_ab_h2fuse_l2pipe.txt): BF16 +1.3 % with H2FUSE,
+    // +1.9 % with both; F16X2 +1.1 % with H2FUSE, and L2PIPE costs it 0.5 % (its widest instantiation then spills 24 bytes) -- so
+    // F16X2 keeps the un-pipelined layer 2.
+    constexpr bool L2PIPE = (NS == 1 || NS == 4) && (C1 / 32) % 2 == 0;      // (F16 [r6]: bf16's layer-1 form, bf16's pipelining)
+    constexpr bool H2FUSE = sab_h2fuse(NS), FRAG_PIPE = sab_frag_pipe(NS);
     using Cfg = SaBCfg<C1, C2, C3, NS>;
-    using PL = Planes<NS>;
     constexpr int NPL = Cfg::NPL;
     constexpr bool F16 = Cfg::F16;
-    constexpr int T2 = Cfg::T2, T3 = Cfg::T3, NC1 = Cfg::NC1, RS2 = Cfg::RS2, RS3 = Cfg::RS3, C2P = Cfg::C2P;
+    constexpr int T2 = Cfg::T2, T3 = Cfg::T3, NC1 = Cfg::NC1;
     constexpr int WBYTES = RES ? Cfg::RES_W : 2 * Cfg::TILE;
     extern __shared__ __attribute__((aligned(16))) char smem[];
     char* wt0 = smem;
@@ -274,7 +200,7 @@ __global__ __launch_bounds__(SAB_THREADS, (sab_min_waves<C1, C2, C3, NS, RES, MO
 #pragma unroll
             for (int j = 0; j < 8; ++j) { unsigned o[1]; split_planes<NS>(k[2 * j], k[2 * j + 1], o); d[j] = o[0]; }
         }
-    } else if constexpr (!ROWS) {
+    } else {
         if (fmode) {
             // A tiles of layer 1: row i = [wh(v0..v7) | wh(v0..v7)] then [wl(v0..v7) | 0], v = (f0..f4, dx, dy, dz), planes of W1f / uf, W1x / ux
             const float iu = F16 ? 1.f / p.u1f : 1.f, iux = F16 ? 1.f / p.u1x : 1.f;      // (powers of two: exact; BF16X3: no plane factor)
@@ -317,20 +243,12 @@ __global__ __launch_bounds__(SAB_THREADS, (sab_min_waves<C1, C2, C3, NS, RES, MO
     // window here, so that an accumulator tile is initialised by four LDS reads and no arithmetic
     float* sbw = F16 ? reinterpret_cast<float*>(smem + WBYTES + Cfg::W1B + T2 * 32 * 4 + 16) + wave * (T2 * 32) : sb2;
 
-    // LDS-DMA of one tile image: each wave instruction moves 1 KiB (64 lanes x 16 B), lane-linear on both sides
-    auto dma_tile = [&](const char* src, char* dst, int bytes) {
-        for (int off = wave * 1024; off < bytes; off += WV * 1024) {
-            if (off + lane * 16 < bytes)
-                __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(src + off + lane * 16),
-                                                 (__attribute__((address_space(3))) void*)(dst + off), 16, 0, 0);
-        }
-    };
     constexpr int CPT = RES ? 1 : Cfg::CPT, UPT = RES ? 1 : Cfg::UPT;
-    auto dma_w2 = [&](int step, char* dst) { dma_tile(p.W2s + (size_t)step * CPT * Cfg::TB2, dst, CPT * Cfg::TB2); };
-    auto dma_w3 = [&](int step, char* dst) { dma_tile(p.W3s + (size_t)step * UPT * Cfg::TB3, dst, UPT * Cfg::TB3); };
+    auto dma_w2 = [&](int step, char* dst) { sab_dma_tile(p.W2s + (size_t)step * CPT * Cfg::TB2, dst, CPT * Cfg::TB2, wave, lane); };
+    auto dma_w3 = [&](int step, char* dst) { sab_dma_tile(p.W3s + (size_t)step * UPT * Cfg::TB3, dst, UPT * Cfg::TB3, wave, lane); };
 
-    // persistent streamed variant (SaBP::pers, set abstraction only): see the comment above the kernel
-    constexpr bool PERS = !RES && !ROWS;
+    // persistent streamed variant (SaBP::pers): see the comment above the kernel
+    constexpr bool PERS = !RES;
     const bool pers = PERS && p.pers;
     if constexpr (PERS) {
         // a workgroup without an octet (the last XCD's range may be shorter than the others'): nothing to do, before any DMA or barrier
@@ -341,8 +259,8 @@ __global__ __launch_bounds__(SAB_THREADS, (sab_min_waves<C1, C2, C3, NS, RES, MO
         if (tid < Cfg::REC_SLOTS) reinterpret_cast<unsigned*>(smem + WBYTES + Cfg::SMALL_NOREC)[tid] = 0u;      // per-window running maxima of the record combine
     }
     if constexpr (RES) {
-        dma_tile(p.W2s, smem, NC1 * Cfg::TB2);
-        dma_tile(p.W3s, smem + NC1 * Cfg::TB2, T3 * Cfg::TB3);
+        sab_dma_tile(p.W2s, smem, NC1 * Cfg::TB2, wave, lane);
+        sab_dma_tile(p.W3s, smem + NC1 * Cfg::TB2, T3 * Cfg::TB3, wave, lane);
     } else {
         dma_w2(0, wt0);
     }
@@ -353,7 +271,7 @@ __global__ __launch_bounds__(SAB_THREADS, (sab_min_waves<C1, C2, C3, NS, RES, MO
     // walks the same ranges an octet -- 8 consecutive groups, one per wave -- at a time.
     const int xcd = blockIdx.x & 7, slot = blockIdx.x >> 3, nbx = RES ? p.nblk >> 3 : (int)(gridDim.x >> 3);
     const int g_end = (RES || pers) ? min(ngroups, (xcd + 1) * p.per_xcd) : ngroups;
-    const int spg = (RES || ROWS) ? 1 : max(1, __builtin_amdgcn_readfirstlane(p.spg)), sw = wave % spg;      // sw: this wave's strip of its group
+    const int spg = RES ? 1 : max(1, __builtin_amdgcn_readfirstlane(p.spg)), sw = wave % spg;      // sw: this wave's strip of its group
     int g = ((RES || pers) ? xcd * p.per_xcd + slot * WV : (spg > 1 ? L * (WV / spg) + wave / spg : L * WV)) + wave * (RES || spg == 1);
     constexpr bool fform = fmode || (L1M && hasfeat);           // layer 1 reads raw feature rows (no table, no producer that chose s1)
     // PERS: what a group needs before its first strip -- centroid, live strips, the window's range record and scale -- is loaded one
@@ -372,15 +290,15 @@ __global__ __launch_bounds__(SAB_THREADS, (sab_min_waves<C1, C2, C3, NS, RES, MO
         h.valid = g_ < ngroups;
         const int gg_ = h.valid ? g_ : ngroups - 1;
         h.b = gg_ / HA(S);
-        h.gf = ROWS ? (size_t)gg_ : (size_t)h.b * HA(S_total) + HA(s_off) + (gg_ - h.b * HA(S));
+        h.gf = (size_t)h.b * HA(S_total) + HA(s_off) + (gg_ - h.b * HA(S));
         return h;
     };
     // Slots >= cnt of a group repeat slot 0 (ball-query padding, pointnet2_utils.py:104-106): 32-slot strips made only of
     // padding cannot change the max and are skipped.  In the streamed variant every wave still walks the tile steps of the
     // workgroup's longest group (DMA pieces and barriers), without computing.
     auto strips_of = [&](Head h) {
-        int n = ROWS ? 1 : HA(K) >> 5;
-        if (!ROWS && HA(cnt)) n = min(n, max(1, (HA(cnt)[h.gf * HA(cnt_ld)] + 31) >> 5));
+        int n = HA(K) >> 5;
+        if (HA(cnt)) n = min(n, max(1, (HA(cnt)[h.gf * HA(cnt_ld)] + 31) >> 5));
         if (spg > 1) n = (h.valid && sw < n) ? 1 : 0;      // spread: this wave owns strip sw of its group (or nothing)
         return n;
     };
@@ -430,14 +348,14 @@ __global__ __launch_bounds__(SAB_THREADS, (sab_min_waves<C1, C2, C3, NS, RES, MO
     const int gg = valid ? g : ngroups - 1;
     const int b = PERS ? hc_b : gg / HA(S);
     // index of this group in the caller's arrays (centroids, index lists, counts, output rows)
-    const size_t gf = PERS ? hc_gf : ROWS ? (size_t)gg : (size_t)b * HA(S_total) + HA(s_off) + (gg - b * HA(S));
+    const size_t gf = PERS ? hc_gf : (size_t)b * HA(S_total) + HA(s_off) + (gg - b * HA(S));
     float mrun[T3];
 #pragma unroll
     for (int u = 0; u < T3; ++u) mrun[u] = -INFINITY;
 
-    float4 ctr = make_float4(0.f, 0.f, 0.f, 0.f);
-    const int32_t* gi = nullptr;
-    if constexpr (!ROWS) { if constexpr (PERS) ctr = ctr_n; else ctr = HA(ctr4)[gf]; gi = HA(gidx) + gf * HA(K) + sw * 32; }
+    float4 ctr;
+    if constexpr (PERS) ctr = ctr_n; else ctr = HA(ctr4)[gf];
+    const int32_t* gi = HA(gidx) + gf * HA(K) + sw * 32;
     // PERS: this octet's head has arrived; the next octet's (same slot of the XCD range, nbx octets on) is requested now
     const int my_strips_pers = strips_n;
     const unsigned hamax = amax_n;
@@ -447,7 +365,6 @@ __global__ __launch_bounds__(SAB_THREADS, (sab_min_waves<C1, C2, C3, NS, RES, MO
     if constexpr (PERS) {
         if (more_oct) { const Head h = head_of(g + nbx * WV); load_head(h); hn_valid = h.valid; hn_b = h.b; hn_gf = h.gf; }
     }
-    const int row0 = ROWS ? (gg - b * HA(S)) * 32 : 0;          // ROWS: first point of this strip inside its window
     unsigned am = 0u;
     // f16x2 range: with P1' = s1 P1 (table stored scaled) and d' = s1 d the layer-1 output is H1' = s1 H1 <= a1 + s1 |W1x|_1 dmax
     // (< 2^15 by the table's choice of s1); layer 2 accumulates (s1 / u2)(W2 H1 + b2); H2' = s2 H2 with the power of two s2 that
@@ -456,11 +373,10 @@ __global__ __launch_bounds__(SAB_THREADS, (sab_min_waves<C1, C2, C3, NS, RES, MO
     // by the table's producer otherwise) so that H1' = s1 H1 AND H2' = (s1 / u2) H2 -- layer 2's accumulators as they are -- stay below
     // 2^15; with u2 = 2^floor(log2 |W2|_1) (pack.hip: chain_unscale) the two bounds agree to a factor 2-4, and one plane loses nothing to a
     // few binades of headroom.  The conversion of H2 is then cvt + packed ReLU + packed clamp, without the two multiplies by c2
-    // (whole step +6.7 % in a timing build, profiles/r6_f16_chain_scale.txt).  The row chains (ROWS) read rows whose scale
-    // their producer chose for the rows alone: they keep the factor.
-    constexpr bool C2ONE = NS == 4 && !ROWS;
+    // (whole step +6.7 % in a timing build, profiles/r6_f16_chain_scale.txt).  (The row chains, row_mlp_bf16.hip, read rows whose
+    // scale their producer chose for the rows alone: they keep the factor.)
+    constexpr bool C2ONE = NS == 4;
     float s1 = 1.f, c2 = HA(u2), c3 = C2ONE ? HA(u3) * HA(u2) : HA(u3);      // (without range arguments: s1 = 1; C2ONE: H2' = H2 / u2 as accumulated)
-    float so = 1.f;                                             // F16 row chain with fp16 output rows: their per-window power of two
     float b1s_f = 1.f, b1s_x = 1.f, b1s_b = 1.f;               // F16 L1M: the B operand's factors s1 a1f, s1 a1x, s1 a1b (wave-uniform)
     if constexpr (F16) {
         if (fform && HA(feat_amax)) {
@@ -472,12 +388,8 @@ __global__ __launch_bounds__(SAB_THREADS, (sab_min_waves<C1, C2, C3, NS, RES, MO
             c2 = HA(u2) * s2 * pow2_inverse(s1);
             c3 = HA(u3) * pow2_inverse(s2);
         } else if (!fform && HA(p1_amax)) {
-            float a1 = __uint_as_float(PERS ? hamax : HA(p1_amax)[b]);
-            if constexpr (DIRECT) {
-                if (NS == 4 && HA(t_bf16)) s1 = HA(row16_scale)[b];                        // fp16 rows: stored with this power of two, the record is of the stored values
-                else { s1 = f16x2_scale(HA(p1_amax)[b]); a1 *= s1; }                     // unscaled input rows: scaled as they are read
-            }
-            else s1 = PERS ? hscale : HA(p1_scale)[b];
+            const float a1 = __uint_as_float(PERS ? hamax : HA(p1_amax)[b]);
+            s1 = PERS ? hscale : HA(p1_scale)[b];
             const float inv_s1 = pow2_inverse(s1);
             const float bh1 = a1 + s1 * (HA(w1x_norm) * HA(dmax));
             const float bh2 = __fmaf_rn(HA(w2_norm), bh1 * inv_s1, HA(b2_max));
@@ -495,16 +407,6 @@ __global__ __launch_bounds__(SAB_THREADS, (sab_min_waves<C1, C2, C3, NS, RES, MO
         s1 = __uint_as_float(__builtin_amdgcn_readfirstlane(__float_as_uint(s1)));
         c2 = __uint_as_float(__builtin_amdgcn_readfirstlane(__float_as_uint(c2)));
         c3 = __uint_as_float(__builtin_amdgcn_readfirstlane(__float_as_uint(c3)));
-        if constexpr (ROWS && NS == 4) {
-            if (HA(out_bf16)) {
-                // fp16 output rows: out' = so out with the power of two so that keeps |W3|_1 bound(H2) + max|b3| below 2^15, bound(H2) =
-                // 2^15 / s2 by the choice of s2 (c3 = u3 / s2).  Folded into the epilogue's factor and bias: out' = acc (c3 so) + b3 so.
-                const float bound2 = 32768.f * (c3 / HA(u3));                             // = 2^15 / s2 >= bound(H2)
-                so = f16x2_scale(__float_as_uint(__fmaf_rn(HA(w3_norm), bound2, HA(b3_max))));
-                so = __uint_as_float(__builtin_amdgcn_readfirstlane(__float_as_uint(so)));
-                if (lane == 0 && valid && row0 == 0) HA(row16_scale)[b] = so;            // (one writer per window: its first strip)
-            }
-        }
         // (PERS: consecutive octets are mostly of one window -- the wave's copies already hold these values when s1 has not changed)
         if (!PERS || s1 != s1_prev) {
             for (int i = lane; i < T2 * 32; i += 64) sbw[i] = sb2[i] * s1;           // read back by this wave only (LDS ops of a wave stay in order)
@@ -536,7 +438,7 @@ __global__ __launch_bounds__(SAB_THREADS, (sab_min_waves<C1, C2, C3, NS, RES, MO
     // (F16X2 and BF16: +0.9 % on the f16x2 step, dominant kernel 1.620 -> 1.576 ms, same-box build A/B profiles/r4_ab_xpf.txt;
     // BF16X3 would spill: its widest instantiation already sits at 256 registers.)
     // PERS: the first gather of the NEXT octet's group is requested during this group's last strip in the same way (pref).
-    constexpr bool XPF = !ROWS && NS != 3;
+    constexpr bool XPF = NS != 3;
     if (XPF && !pref) {
         idx_cur = gi[l31];
         q_cur = p.pts4[(size_t)b * p.Npts + idx_cur];
@@ -570,136 +472,85 @@ __global__ __launch_bounds__(SAB_THREADS, (sab_min_waves<C1, C2, C3, NS, RES, MO
         // may come from the matrix pipe (BF16, F16X2 feature mode) or from the VALU without changing the W2 images (W2PERM)
         auto qi = [&](int j4) { return 2 * j4 + half; };
         const float4* prow = nullptr;
-        const float4* trow[3] = {nullptr, nullptr, nullptr};       // ROWS: the three table rows of this lane's point ...
-        float tw[3] = {0.f, 0.f, 0.f};                             // ... and their inverse-distance weights
         u32x4 b1f = {0u, 0u, 0u, 0u};                      // L1M / L1F: the B operand of the layer-1 MFMA
         u32x4 b1g = {0u, 0u, 0u, 0u};                      // L1F, BF16X3: the second one ([x0 | x2])
         float cj = 1.f;                                    // L1F: s1 / kappa_j of this lane's neighbour
-        // ROWS: raw = (w0 T0 + w1 T1) + w2 T2 of chunk c (pointnet2_utils.py:303 applied to the layer-1 table; the table is stored
-        // scaled by s1 in F16X2, so the blend is s1 H1 before the ReLU)
-        f32x4 trw[ROWS ? 3 : 1][4];
-        auto fetch = [&](int c) {                   // issue the loads of chunk c's three table rows
-#pragma unroll
-            for (int j = 0; j < ((ROWS && !DIRECT) ? 3 : 1); ++j)
-#pragma unroll
-                for (int j4 = 0; j4 < 4; ++j4) {
-                    if constexpr ((NS == 1 || NS == 4) && DIRECT) {
-                        if (p.t_bf16) {          // 4 bf16 / fp16 values = 8 bytes at value offset 32 c + 4 qi(j4) of this lane's row
-                            const uint2 h = *reinterpret_cast<const uint2*>(reinterpret_cast<const char*>(trow[j]) + (size_t)(c * 32 + 4 * qi(j4)) * 2);
-                            if constexpr (NS == 1) {
-                                trw[j][j4] = f32x4{__uint_as_float(h.x << 16), __uint_as_float(h.x & 0xffff0000u), __uint_as_float(h.y << 16),
-                                                   __uint_as_float(h.y & 0xffff0000u)};
-                            } else {             // widened exactly; finish_slice converts back to the same fp16 values (they ARE the plane)
-                                const f16x2 a = __builtin_bit_cast(f16x2, h.x), b_ = __builtin_bit_cast(f16x2, h.y);
-                                trw[j][j4] = f32x4{(float)a[0], (float)a[1], (float)b_[0], (float)b_[1]};
-                            }
-                            continue;
-                        }
-                    }
-                    trw[j][j4] = *reinterpret_cast<const f32x4*>(trow[j] + c * 8 + qi(j4));
-                }
-        };
-        auto blend = [&]() {
-#pragma unroll
-            for (int j4 = 0; j4 < 4; ++j4)
-#pragma unroll
-                for (int e = 0; e < 4; ++e)
-                    raw[j4][e] = DIRECT ? ((F16 && !(NS == 4 && p.t_bf16)) ? trw[0][j4][e] * s1 : trw[0][j4][e])       // (fp16 rows arrive scaled)
-                                        : __fmaf_rn(tw[2], trw[ROWS ? 2 : 0][j4][e], __fmaf_rn(tw[1], trw[ROWS ? 1 : 0][j4][e], __fmul_rn(tw[0], trw[0][j4][e])));
-        };
-        if constexpr (DIRECT) {
-            trow[0] = ((NS == 1 || NS == 4) && p.t_bf16)
-                          ? reinterpret_cast<const float4*>(reinterpret_cast<const char*>(p.P1) + ((size_t)b * p.N + min(row0 + l31, p.N - 1)) * p.ldp * 2)
-                          : reinterpret_cast<const float4*>(p.P1 + ((size_t)b * p.N + min(row0 + l31, p.N - 1)) * p.ldp);
-            fetch(0);
-            blend();
-        } else if constexpr (ROWS) {
-            const size_t gr = ((size_t)b * p.N + min(row0 + l31, p.N - 1)) * 3;
-#pragma unroll
-            for (int j = 0; j < 3; ++j) {
-                trow[j] = reinterpret_cast<const float4*>(p.P1 + ((size_t)b * p.Npts + p.nn_idx[gr + j]) * p.ldp);
-                tw[j] = p.nn_w[gr + j];
-            }
-            fetch(0);
-            blend();
-        } else {
-            const int idx = XPF ? idx_cur : gi[strip * 32 + l31];
-            const float4 q = XPF ? q_cur : p.pts4[(size_t)b * p.Npts + idx];
-            if constexpr (XPF) idx_nxt = (strip + 1 < my_strips) ? gi[(strip + 1) * 32 + l31] : (more_oct ? p.gidx[hn_gf * p.K + l31] : idx_cur);
-            dx = __fsub_rn(q.x, ctr.x); dy = __fsub_rn(q.y, ctr.y); dz = __fsub_rn(q.z, ctr.z);
-            if constexpr (F16 && !L1M) { if (!fmode) { dx *= s1; dy *= s1; dz *= s1; } }      // exact; with P1' = s1 P1 this makes layer 1 produce s1 H1
-            if (fmode) {
-                if constexpr (L1F && NS == 3) {
-                    // (no XPF in this mode: the feature row is requested here)  B1f = [x0 | x1], B1g = [x0 | x2] of v = (f0..f4, dx, dy, dz)
-                    const float4* fr = reinterpret_cast<const float4*>(p.feat + ((size_t)b * p.Npts + idx) * p.ldf);
-                    const float4 fa = fr[0], fb = fr[1];
-                    const float v[8] = {fa.x, fa.y, fa.z, fa.w, fb.x, dx, dy, dz};
-#pragma unroll
-                    for (int w = 0; w < 4; ++w) {
-                        unsigned o[3];
-                        split_planes<3>(v[2 * w], v[2 * w + 1], o);
-                        b1f[w] = half ? o[1] : o[0];
-                        b1g[w] = half ? o[2] : o[0];
-                    }
-                }
-                if constexpr (L1F && F16) {
-                    // B1 = [xh(v0..v7) | xl(v0..v7)], v = (f0..f4, dx, dy, dz) of this lane's neighbour times its own power of two s_j
-                    float v[8] = {f0_cur.x, f0_cur.y, f0_cur.z, f0_cur.w, f1_cur.x, dx, dy, dz};
-                    const float af = fmaxf(fmaxf(fmaxf(fabsf(v[0]), fabsf(v[1])), fmaxf(fabsf(v[2]), fabsf(v[3]))), fabsf(v[4]));
-                    const float ax = fmaxf(fmaxf(fabsf(v[5]), fabsf(v[6])), fabsf(v[7]));
-                    const float kap = fminf(f16x2_scale(__float_as_uint(af)) * (1.f / p.u1f), f16x2_scale(__float_as_uint(ax)) * (1.f / p.u1x));
-                    const float sgf = kap * p.u1f, sgx = kap * p.u1x;
-                    cj = s1 * pow2_inverse(kap);
-#pragma unroll
-                    for (int j = 0; j < 5; ++j) v[j] *= sgf;
-#pragma unroll
-                    for (int j = 5; j < 8; ++j) v[j] *= sgx;
-#pragma unroll
-                    for (int w = 0; w < 4; ++w) {
-                        unsigned o[2];
-                        split_planes<2>(v[2 * w], v[2 * w + 1], o);
-                        b1f[w] = half ? o[1] : o[0];
-                    }
-                }
-            } else if constexpr (L1M) {
-                // B1: this lane's 8 k slots of its neighbour (half 0: k 0..7, half 1: k 8..15), hi / lo bf16 planes of the inputs
-                float f[8];
-#pragma unroll
-                for (int j = 0; j < 8; ++j) f[j] = 0.f;
-                if (hasfeat) {
-                    f[0] = f0_cur.x; f[1] = f0_cur.y; f[2] = f0_cur.z; f[3] = f0_cur.w; f[4] = f1_cur.x;
-                    if constexpr (F16) {
-#pragma unroll
-                        for (int j = 0; j < 5; ++j) f[j] *= b1s_f;          // exact (power of two); < 2^8 by the choice of s1 and a1f
-                    }
-                } else {
-                    prow = reinterpret_cast<const float4*>(p.P1 + ((size_t)b * p.Npts + idx) * p.ldp);
-                    if (strip == 0 && !pref) {          // (later strips: requested during the previous strip's layer 3)
-#pragma unroll
-                        for (int j4 = 0; j4 < 4; ++j4) raw[j4] = *reinterpret_cast<const f32x4*>(prow + qi(j4));
-                    }
-                }
-                // x minus its high 16-bit plane (bf16 / fp16, round to nearest even): exact
-                auto lo_of = [](float x) {
-                    if constexpr (F16) return x - (float)(_Float16)x;
-                    else return x - __uint_as_float(__builtin_bit_cast(unsigned, __builtin_convertvector(f32x2{x, 0.f}, bf16x2)) << 16);
-                };
-                const float ex = F16 ? dx * b1s_x : dx, ey = F16 ? dy * b1s_x : dy, ez = F16 ? dz * b1s_x : dz;
-                const float va[8] = {f[0], f[1], f[2], f[3], f[4], lo_of(ex), lo_of(ey), lo_of(ez)};
-                // (the constant slot that carries b1: unused in table mode -- its A entry is 0 -- and there s1 alone may exceed fp16: 0 x inf)
-                const float vb[8] = {ex, ey, ez, F16 ? (hasfeat ? b1s_b : 0.f) : 1.f, lo_of(f[0]), lo_of(f[1]), lo_of(f[2]), lo_of(f[3])};
+        const int idx = XPF ? idx_cur : gi[strip * 32 + l31];
+        const float4 q = XPF ? q_cur : p.pts4[(size_t)b * p.Npts + idx];
+        if constexpr (XPF) idx_nxt = (strip + 1 < my_strips) ? gi[(strip + 1) * 32 + l31] : (more_oct ? p.gidx[hn_gf * p.K + l31] : idx_cur);
+        dx = __fsub_rn(q.x, ctr.x); dy = __fsub_rn(q.y, ctr.y); dz = __fsub_rn(q.z, ctr.z);
+        if constexpr (F16 && !L1M) { if (!fmode) { dx *= s1; dy *= s1; dz *= s1; } }      // exact; with P1' = s1 P1 this makes layer 1 produce s1 H1
+        if (fmode) {
+            if constexpr (L1F && NS == 3) {
+                // (no XPF in this mode: the feature row is requested here)  B1f = [x0 | x1], B1g = [x0 | x2] of v = (f0..f4, dx, dy, dz)
+                const float4* fr = reinterpret_cast<const float4*>(p.feat + ((size_t)b * p.Npts + idx) * p.ldf);
+                const float4 fa = fr[0], fb = fr[1];
+                const float v[8] = {fa.x, fa.y, fa.z, fa.w, fb.x, dx, dy, dz};
 #pragma unroll
                 for (int w = 0; w < 4; ++w) {
-                    unsigned o[1];
-                    split_planes<NS>(half ? vb[2 * w] : va[2 * w], half ? vb[2 * w + 1] : va[2 * w + 1], o);
-                    b1f[w] = o[0];
+                    unsigned o[3];
+                    split_planes<3>(v[2 * w], v[2 * w + 1], o);
+                    b1f[w] = half ? o[1] : o[0];
+                    b1g[w] = half ? o[2] : o[0];
+                }
+            }
+            if constexpr (L1F && F16) {
+                // B1 = [xh(v0..v7) | xl(v0..v7)], v = (f0..f4, dx, dy, dz) of this lane's neighbour times its own power of two s_j
+                float v[8] = {f0_cur.x, f0_cur.y, f0_cur.z, f0_cur.w, f1_cur.x, dx, dy, dz};
+                const float af = fmaxf(fmaxf(fmaxf(fabsf(v[0]), fabsf(v[1])), fmaxf(fabsf(v[2]), fabsf(v[3]))), fabsf(v[4]));
+                const float ax = fmaxf(fmaxf(fabsf(v[5]), fabsf(v[6])), fabsf(v[7]));
+                const float kap = fminf(f16x2_scale(__float_as_uint(af)) * (1.f / p.u1f), f16x2_scale(__float_as_uint(ax)) * (1.f / p.u1x));
+                const float sgf = kap * p.u1f, sgx = kap * p.u1x;
+                cj = s1 * pow2_inverse(kap);
+#pragma unroll
+                for (int j = 0; j < 5; ++j) v[j] *= sgf;
+#pragma unroll
+                for (int j = 5; j < 8; ++j) v[j] *= sgx;
+#pragma unroll
+                for (int w = 0; w < 4; ++w) {
+                    unsigned o[2];
+                    split_planes<2>(v[2 * w], v[2 * w + 1], o);
+                    b1f[w] = half ? o[1] : o[0];
+                }
+            }
+        } else if constexpr (L1M) {
+            // B1: this lane's 8 k slots of its neighbour (half 0: k 0..7, half 1: k 8..15), hi / lo bf16 planes of the inputs
+            float f[8];
+#pragma unroll
+            for (int j = 0; j < 8; ++j) f[j] = 0.f;
+            if (hasfeat) {
+                f[0] = f0_cur.x; f[1] = f0_cur.y; f[2] = f0_cur.z; f[3] = f0_cur.w; f[4] = f1_cur.x;
+                if constexpr (F16) {
+#pragma unroll
+                    for (int j = 0; j < 5; ++j) f[j] *= b1s_f;          // exact (power of two); < 2^8 by the choice of s1 and a1f
                 }
             } else {
                 prow = reinterpret_cast<const float4*>(p.P1 + ((size_t)b * p.Npts + idx) * p.ldp);
-                if (!XPF || (strip == 0 && !pref)) {
+                if (strip == 0 && !pref) {          // (later strips: requested during the previous strip's layer 3)
 #pragma unroll
                     for (int j4 = 0; j4 < 4; ++j4) raw[j4] = *reinterpret_cast<const f32x4*>(prow + qi(j4));
                 }
+            }
+            // x minus its high 16-bit plane (bf16 / fp16, round to nearest even): exact
+            auto lo_of = [](float x) {
+                if constexpr (F16) return x - (float)(_Float16)x;
+                else return x - __uint_as_float(__builtin_bit_cast(unsigned, __builtin_convertvector(f32x2{x, 0.f}, bf16x2)) << 16);
+            };
+            const float ex = F16 ? dx * b1s_x : dx, ey = F16 ? dy * b1s_x : dy, ez = F16 ? dz * b1s_x : dz;
+            const float va[8] = {f[0], f[1], f[2], f[3], f[4], lo_of(ex), lo_of(ey), lo_of(ez)};
+            // (the constant slot that carries b1: unused in table mode -- its A entry is 0 -- and there s1 alone may exceed fp16: 0 x inf)
+            const float vb[8] = {ex, ey, ez, F16 ? (hasfeat ? b1s_b : 0.f) : 1.f, lo_of(f[0]), lo_of(f[1]), lo_of(f[2]), lo_of(f[3])};
+#pragma unroll
+            for (int w = 0; w < 4; ++w) {
+                unsigned o[1];
+                split_planes<NS>(half ? vb[2 * w] : va[2 * w], half ? vb[2 * w + 1] : va[2 * w + 1], o);
+                b1f[w] = o[0];
+            }
+        } else {
+            prow = reinterpret_cast<const float4*>(p.P1 + ((size_t)b * p.Npts + idx) * p.ldp);
+            if (!XPF || (strip == 0 && !pref)) {
+#pragma unroll
+                for (int j4 = 0; j4 < 4; ++j4) raw[j4] = *reinterpret_cast<const f32x4*>(prow + qi(j4));
             }
         }
         // layer 1 of chunk c on the matrix pipe.  BF16: one MFMA (C = the table row in table mode); F16X2 feature mode: the two
@@ -809,68 +660,8 @@ __global__ __launch_bounds__(SAB_THREADS, (sab_min_waves<C1, C2, C3, NS, RES, MO
                 f32x4 v;
 #pragma unroll
                 for (int e = 0; e < 4; ++e)
-                    v[e] = ROWS ? raw[j4][e] : __fmaf_rn(wz[e], dz, __fmaf_rn(wy[e], dy, __fmaf_rn(wx[e], dx, raw[j4][e])));
-                unsigned lo[NPL], hi[NPL];
-                if constexpr (DIRECT) {                  // the rows are the layer's input as it is (|v| < 2^15 by the scale)
-                    split_planes<NS>(v[0], v[1], lo);
-                    split_planes<NS>(v[2], v[3], hi);
-                } else if constexpr (NS == 1) {
-                    split_planes<NS>(v[0], v[1], lo);
-                    split_planes<NS>(v[2], v[3], hi);
-                    lo[0] = relu_pk_bf16(lo[0]); hi[0] = relu_pk_bf16(hi[0]);
-                } else if constexpr (F16) {
-                    split_planes<NS>(relu_sat_f16(v[0]), relu_sat_f16(v[1]), lo);
-                    split_planes<NS>(relu_sat_f16(v[2]), relu_sat_f16(v[3]), hi);
-                } else {
-                    split_planes<NS>(relu_bits(v[0]), relu_bits(v[1]), lo);
-                    split_planes<NS>(relu_bits(v[2]), relu_bits(v[3]), hi);
-                }
-#pragma unroll
-                for (int s = 0; s < NPL; ++s) {
-                    bp[j4 >> 1][s][(j4 & 1) * 2 + 0] = lo[s];
-                    bp[j4 >> 1][s][(j4 & 1) * 2 + 1] = hi[s];
-                }
-            }
-        };
-        // the MFMAs of one chunk: the 2*T2 (k-block m, tile t) groups are taken two at a time and their MFMAs alternate between the
-        // two tiles' accumulators: anything issued between two MFMAs on the SAME accumulator (here the next fragment reads) costs
-        // ~43 cycles, between MFMAs on different accumulators ~6 (MI355X_MICROARCH.md, latency table)
-        // FRAG_PIPE (BF16): the fragment reads of group pr + 1 are issued BEFORE the MFMAs of group pr (two register sets, order
-        // pinned with scheduling barriers).  Left to itself the compiler emitted read, read, s_waitcnt lgkmcnt(0), MFMA, MFMA per
-        // group -- the full LDS latency in front of every MFMA pair, which with ONE product per operand pair is most of a tile
-        // step (phase timeline, profiles/r4_sa_timeline.txt: 1.0-1.7 us per 14-MFMA chunk whose MFMAs take 0.22 us).
-        // between(pr) runs after the MFMAs of pair pr were issued (L2PIPE: slices of the next chunk's layer-1 finish).
-        auto mfma_groups = [&](const char* cur, u32x4 (&bp)[2][NPL], auto&& between) {
-            const char* pa = cur + l31 * RS2 + (16 * half) * 2;
-            auto ld2 = [&](int pr, u32x4 (&x0)[NPL], u32x4 (&x1)[NPL]) {
-                const int m0 = (2 * pr) / T2, t0 = (2 * pr) % T2, m1 = (2 * pr + 1) / T2, t1 = (2 * pr + 1) % T2;
-#pragma unroll
-                for (int s = 0; s < NPL; ++s) {
-                    x0[s] = *reinterpret_cast<const u32x4*>(pa + 32 * t0 * RS2 + s * 64 + m0 * 16);
-                    x1[s] = *reinterpret_cast<const u32x4*>(pa + 32 * t1 * RS2 + s * 64 + m1 * 16);
-                }
-            };
-            u32x4 fa[2][2][NPL];
-            if constexpr (FRAG_PIPE) ld2(0, fa[0][0], fa[0][1]);
-#pragma unroll
-            for (int pr = 0; pr < T2; ++pr) {
-                const int m0 = (2 * pr) / T2, t0 = (2 * pr) % T2, m1 = (2 * pr + 1) / T2, t1 = (2 * pr + 1) % T2;
-                if constexpr (FRAG_PIPE) {
-                    if (pr + 1 < T2) ld2(pr + 1, fa[(pr + 1) & 1][0], fa[(pr + 1) & 1][1]);
-                    __builtin_amdgcn_sched_barrier(0);
-                } else {
-                    ld2(pr, fa[pr & 1][0], fa[pr & 1][1]);
-                }
-                u32x4 (&a0)[NPL] = fa[pr & 1][0];
-                u32x4 (&a1)[NPL] = fa[pr & 1][1];
-#pragma unroll
-                for (int j = 0; j < PL::NPROD; ++j) {
-                    // PACK4: the last tile's high-plane image carries its low plane in rows 8..11 (see SaBCfg)
-                    if (!(Cfg::PACK4 && t0 == T2 - 1 && PL::A[j] == 1)) h2[t0] = mfma_planes<NS>(a0[PL::A[j]], bp[m0][PL::B[j]], h2[t0]);
-                    if (!(Cfg::PACK4 && t1 == T2 - 1 && PL::A[j] == 1)) h2[t1] = mfma_planes<NS>(a1[PL::A[j]], bp[m1][PL::B[j]], h2[t1]);
-                }
-                if constexpr (FRAG_PIPE) __builtin_amdgcn_sched_barrier(0);
-                between(pr);
+                    v[e] = __fmaf_rn(wz[e], dz, __fmaf_rn(wy[e], dy, __fmaf_rn(wx[e], dx, raw[j4][e])));
+                sab_split_slice<NS, true>(v, j4, bp);
             }
         };
         auto l2_dma = [&](int c) {                      // the next tile step's image into the other buffer
@@ -899,17 +690,12 @@ __global__ __launch_bounds__(SAB_THREADS, (sab_min_waves<C1, C2, C3, NS, RES, MO
                 l2_dma(c);
 #pragma unroll
                 for (int j4 = 0; j4 < 4; ++j4) finish_slice(c, j4, bpA);
-                if constexpr (ROWS) {
-                    if (c + 1 < NC1) fetch(c + 1);      // in flight under this chunk's MFMAs, blended after them
-                } else if (!L1M && !fmode && c + 1 < NC1) {
+                if (!L1M && !fmode && c + 1 < NC1) {
 #pragma unroll
                     for (int j4 = 0; j4 < 4; ++j4) raw[j4] = *reinterpret_cast<const f32x4*>(prow + (c + 1) * 8 + qi(j4));
                 }
                 STAMP(3 + 4 * c);
-                mfma_groups(cur, bpA, [](int) {});
-                if constexpr (ROWS) {
-                    if (c + 1 < NC1) blend();
-                }
+                sab_mfma_groups<Cfg, NS>(cur, l31, half, bpA, h2, [](int) {});
                 if constexpr (L1F) {
                     if (fmode && c + 1 < NC1) d1 = layer1(c + 1);
                 }
@@ -953,7 +739,7 @@ __global__ __launch_bounds__(SAB_THREADS, (sab_min_waves<C1, C2, C3, NS, RES, MO
                     }
                 }
                 STAMP(3 + 4 * c);
-                mfma_groups(cur, bc, [&](int pr) {
+                sab_mfma_groups<Cfg, NS>(cur, l31, half, bc, h2, [&](int pr) {
                     if (more) {
 #pragma unroll
                         for (int j4 = 0; j4 < 4; ++j4) {
@@ -1002,41 +788,8 @@ __global__ __launch_bounds__(SAB_THREADS, (sab_min_waves<C1, C2, C3, NS, RES, MO
         }
         // ReLU in fp32 (the bias is already in), then split in place: h2p[s][t][k] packs D2 rows (2k, 2k+1) of tile t
         u32x4 h2p[NPL][T2][2];        // [plane][tile][k-block m]: directly in MFMA A-operand form
-        // one k-block (8 channels per lane) of tile t; PACK4: the last tile's block 0 is re-packed once both planes exist
-        auto split_half = [&](int t, int m) {
-#pragma unroll
-            for (int k = 4 * m; k < 4 * m + 4; ++k) {
-                unsigned o[NPL];
-                if constexpr (C2ONE) {      // (c2 = 1)
-                    // cvt + one packed integer max, as in BF16.  No clamp: the bound behind s1 is rigorous, and a caller who breaks the
-                    // contract behind it (dmax) gets inf -> NaN outputs instead of silently clamped ones.  (Same-box A/B, whole step,
-                    // profiles/r6_f16_chain_scale.txt: a factor per layer 40 630, chain scale 41 200, without the clamps 41 740 windows/s.)
-                    split_planes<NS>(h2[t][2 * k], h2[t][2 * k + 1], o);
-                    o[0] = relu_pk_bf16(o[0]);
-                }
-                else if constexpr (F16) split_planes<NS>(relu_sat_f16(h2[t][2 * k] * c2), relu_sat_f16(h2[t][2 * k + 1] * c2), o);
-                else if constexpr (NS == 1) { split_planes<NS>(h2[t][2 * k], h2[t][2 * k + 1], o); o[0] = relu_pk_bf16(o[0]); }     // (u2 = 1: no factor)
-                else split_planes<NS>(relu_bits(h2[t][2 * k] * c2), relu_bits(h2[t][2 * k + 1] * c2), o);
-#pragma unroll
-                for (int s = 0; s < NPL; ++s) h2p[s][t][k >> 2][k & 3] = o[s];
-            }
-            if constexpr (Cfg::PACK4) {
-                if (t == T2 - 1 && m == 0) {
-                    // last k-block: slots [xh(4) | xl(4)] in the lower half-wave, [xh(4) | 0] in the upper one (which gets the values from
-                    // its partner lane: same neighbour, other half); the packer stores [wh | wh | wl | 0] at these positions of the W3 image
-                    const unsigned h01 = h2p[0][T2 - 1][0][0], h23 = h2p[0][T2 - 1][0][1];
-                    const unsigned l01 = h2p[1][T2 - 1][0][0], l23 = h2p[1][T2 - 1][0][1];
-                    const unsigned ph01 = (unsigned)__shfl_xor((int)h01, 32, 64), ph23 = (unsigned)__shfl_xor((int)h23, 32, 64);
-                    h2p[0][T2 - 1][0][0] = half ? ph01 : h01;
-                    h2p[0][T2 - 1][0][1] = half ? ph23 : h23;
-                    h2p[0][T2 - 1][0][2] = half ? 0u : l01;
-                    h2p[0][T2 - 1][0][3] = half ? 0u : l23;
-                }
-            }
-        };
-        // H2FUSE: only tile 0 is split here; tile t + 1 is split between the MFMA groups of tile t in the FIRST layer-3 step, so that
-        // the conversion (VALU) of one wave runs under the MFMAs of its SIMD partner instead of both waves converting while the matrix
-        // pipe idles (phase timeline: "h2 ReLU + split" was 8 % of a strip).  Same values, same order of the contraction.
+        auto split_half = [&](int t, int m) { sab_split_half<Cfg, NS, C2ONE>(t, m, half, c2, h2, h2p); };
+        // H2FUSE: only tile 0 is split here, tile t + 1 between the MFMA groups of tile t in the first layer-3 step
 #pragma unroll
         for (int t = 0; t < (H2FUSE ? 1 : T2); ++t) { split_half(t, 0); split_half(t, 1); }
         STAMP(39);
@@ -1055,8 +808,7 @@ __global__ __launch_bounds__(SAB_THREADS, (sab_min_waves<C1, C2, C3, NS, RES, MO
         };
         // TPS = 2 (two tiles resident per step: every MLP but 32-32-64): the two tiles' accumulators take alternate MFMAs (consecutive
         // MFMAs never depend on each other) and share the activation fragments; TPS = 1: one tile, two accumulators that are summed
-        // (the row chains keep one tile at a time: their store addresses would not fit the scalar registers twice)
-        constexpr int TPS = (!ROWS && (RES || UPT == 2)) ? 2 : 1;
+        constexpr int TPS = (RES || UPT == 2) ? 2 : 1;
         static_assert(T3 % TPS == 0, "layer-3 tiles are walked in pairs");
         auto l3_step = [&](int u, auto first_tag) {
             constexpr bool FIRST = decltype(first_tag)::value;
@@ -1070,62 +822,16 @@ __global__ __launch_bounds__(SAB_THREADS, (sab_min_waves<C1, C2, C3, NS, RES, MO
                     if (more_w3) dma_w3(u / UPT + 1, nxt); else if (more) dma_w2(0, nxt);
                 }
             }
-            float b3u = 0.f;
-            if constexpr (ROWS) b3u = p.b3[32 * u + l31];      // (requested here, used after the step's MFMAs)
             f32x16 acc, acc1;
-#pragma unroll
-            for (int r = 0; r < 16; ++r) { acc[r] = 0.f; acc1[r] = 0.f; }
-            const char* pb = cur + l31 * RS3 + (8 * half) * 2;
-            constexpr int NG3 = 2 * (T2 - 1) + Cfg::M_LAST;       // live (tile, k-block) groups of the contraction
-            auto ld3 = [&](int g, u32x4 (&x)[NPL], u32x4 (&x1)[TPS == 2 ? NPL : 1]) {
-#pragma unroll
-                for (int s = 0; s < NPL; ++s) {
-                    x[s] = *reinterpret_cast<const u32x4*>(pb + s * (C2P * 2) + (16 * g) * 2);
-                    if constexpr (TPS == 2) x1[s] = *reinterpret_cast<const u32x4*>(pb + Cfg::TB3 + s * (C2P * 2) + (16 * g) * 2);
-                }
-            };
-            u32x4 fw[2][NPL], fw1[2][TPS == 2 ? NPL : 1];
-            if constexpr (FRAG_PIPE) ld3(0, fw[0], fw1[0]);
-#pragma unroll
-            for (int t = 0; t < T2; ++t) {
-#pragma unroll
-                for (int m = 0; m < 2; ++m) {
-                    if (t < T2 - 1 || m < Cfg::M_LAST) {
-                        const int g = 2 * t + m;
-                        if constexpr (FRAG_PIPE) {
-                            if (g + 1 < NG3) ld3(g + 1, fw[(g + 1) & 1], fw1[(g + 1) & 1]);
-                            __builtin_amdgcn_sched_barrier(0);
-                        } else {
-                            ld3(g, fw[g & 1], fw1[g & 1]);
-                        }
-                        u32x4 a[NPL];
-                        u32x4 (&w)[NPL] = fw[g & 1];
-                        u32x4 (&w1)[TPS == 2 ? NPL : 1] = fw1[g & 1];
-#pragma unroll
-                        for (int s = 0; s < NPL; ++s) a[s] = h2p[s][t][m];
-                        // operand roles swapped w.r.t. layer 2: activations are A, weights are B
-#pragma unroll
-                        for (int j = 0; j < PL::NPROD; ++j) {
-                            if (Cfg::PACK4 && t == T2 - 1 && !(PL::A[j] == 0 && PL::B[j] == 0)) continue;   // one MFMA holds all three products
-                            if constexpr (TPS == 2) {
-                                acc = mfma_planes<NS>(a[PL::A[j]], w[PL::B[j]], acc);
-                                acc1 = mfma_planes<NS>(a[PL::A[j]], w1[PL::B[j]], acc1);
-                            } else {
-                                if (((2 * t + m) * PL::NPROD + j) & 1) acc1 = mfma_planes<NS>(a[PL::A[j]], w[PL::B[j]], acc1);
-                                else acc = mfma_planes<NS>(a[PL::A[j]], w[PL::B[j]], acc);
-                            }
-                        }
-                        if constexpr (FRAG_PIPE) __builtin_amdgcn_sched_barrier(0);
-                        if constexpr (FIRST) {
-                            if (t + 1 < T2) {
-                                if constexpr (!FRAG_PIPE) __builtin_amdgcn_sched_barrier(0);
-                                split_half(t + 1, m);
-                                __builtin_amdgcn_sched_barrier(0);
-                            }
-                        }
+            sab_l3_mfma<Cfg, NS, TPS>(cur, l31, half, h2p, acc, acc1, [&](int t, int m) {
+                if constexpr (FIRST) {
+                    if (t + 1 < T2) {
+                        if constexpr (!FRAG_PIPE) __builtin_amdgcn_sched_barrier(0);
+                        split_half(t + 1, m);
+                        __builtin_amdgcn_sched_barrier(0);
                     }
                 }
-            }
+            });
             STAMP(41 + 4 * u);
             if constexpr (TPS == 2) {
                 finish_tile(u, acc);
@@ -1133,36 +839,7 @@ __global__ __launch_bounds__(SAB_THREADS, (sab_min_waves<C1, C2, C3, NS, RES, MO
             } else {
 #pragma unroll
                 for (int r = 0; r < 16; ++r) acc[r] += acc1[r];
-                if constexpr (ROWS) {
-                    // D3[point][channel]: this lane holds channel 32u + l31 of the points 8(r/4) + 4 half + r%4 -- one store
-                    // instruction writes two 128-byte row segments
-                    float* orow = p.out + ((size_t)b * p.N + row0 + 4 * half) * p.ldo + 32 * u + l31;
-                    const bool colok = valid && (32 * u + l31 < p.ncols);
-                    float* ocm = p.out_cm ? p.out_cm + (size_t)b * p.out_cm_stride + (size_t)(32 * u + l31) * p.N + row0 + 4 * half : nullptr;
-    #pragma unroll
-                    for (int r = 0; r < 16; ++r) {
-                        const int pt = 8 * (r >> 2) + (r & 3);
-                        float o = acc[r] * c3 + b3u;
-                        if (p.relu_out) o = fmaxf(o, 0.f);
-                        if (colok && row0 + 4 * half + pt < p.N) {
-                            if (NS == 1 && p.out_bf16) {
-                                unsigned short* o16 = reinterpret_cast<unsigned short*>(p.out) + ((size_t)b * p.N + row0 + 4 * half + pt) * p.ldo + 32 * u + l31;
-                                *o16 = (unsigned short)(__builtin_bit_cast(unsigned, __builtin_convertvector(f32x2{o, 0.f}, bf16x2)) & 0xffffu);
-                            } else if (NS == 4 && p.out_bf16) {
-                                o = fminf(o * so, 65504.f);              // (exact power of two; the bound keeps it below 2^15 -- the clamp is for a broken contract)
-                                unsigned short* o16 = reinterpret_cast<unsigned short*>(p.out) + ((size_t)b * p.N + row0 + 4 * half + pt) * p.ldo + 32 * u + l31;
-                                const _Float16 h16 = (_Float16)o;
-                                *o16 = __builtin_bit_cast(unsigned short, h16);
-                                o = (float)h16;                          // the record is of the STORED values
-                            } else
-                            orow[(size_t)pt * p.ldo] = o;
-                            if (ocm) ocm[pt] = o;
-                            am = max(am, abs_bits(o));
-                        }
-                    }
-                } else {
-                    finish_tile(u, acc);
-                }
+                finish_tile(u, acc);
             }
             STAMP(42 + 4 * u);
             if constexpr (!RES) {
@@ -1180,7 +857,7 @@ __global__ __launch_bounds__(SAB_THREADS, (sab_min_waves<C1, C2, C3, NS, RES, MO
         STAMP(37);
     }
     if constexpr (PERS) asm volatile("" : "+s"(pk));
-    if constexpr (!ROWS && !RES) {
+    if constexpr (!RES) {
         if (spg > 1) {
             // combine the strips' partial maxima: [wave][C3] floats in the (now idle) tile buffer; the group's first wave finishes
             float* smax = reinterpret_cast<float*>(smem);
@@ -1200,22 +877,18 @@ __global__ __launch_bounds__(SAB_THREADS, (sab_min_waves<C1, C2, C3, NS, RES, MO
             }
         }
     }
-    if constexpr (!ROWS) {
 #pragma unroll
-        for (int u = 0; u < T3; ++u) {
-            const float v = fmaxf(mrun[u], __shfl_xor(mrun[u], 32, 64));
-            if (valid && half == 0 && sw == 0) {
-                float o = fmaxf(v * c3 + (PERS ? sb3[32 * u + l31] : HA(b3)[32 * u + l31]), 0.f);
-                if constexpr (C2ONE) o = (c3 == c3) ? o : c3;          // (fmaxf drops a NaN: the broken-contract marker must reach the caller)
-                HA(out)[gf * HA(ldo) + 32 * u + l31] = o;
-                am = max(am, __float_as_uint(o));
-            }
+    for (int u = 0; u < T3; ++u) {
+        const float v = fmaxf(mrun[u], __shfl_xor(mrun[u], 32, 64));
+        if (valid && half == 0 && sw == 0) {
+            float o = fmaxf(v * c3 + (PERS ? sb3[32 * u + l31] : HA(b3)[32 * u + l31]), 0.f);
+            if constexpr (C2ONE) o = (c3 == c3) ? o : c3;          // (fmaxf drops a NaN: the broken-contract marker must reach the caller)
+            HA(out)[gf * HA(ldo) + 32 * u + l31] = o;
+            am = max(am, __float_as_uint(o));
         }
     }
-    if constexpr (!ROWS) {
-        if (HA(xyz_out) && valid && sw == 0 && lane < 8)
-            HA(xyz_out)[gf * HA(xyz_ld) + lane] = lane == 0 ? ctr.x : lane == 1 ? ctr.y : lane == 2 ? ctr.z : 0.f;
-    }
+    if (HA(xyz_out) && valid && sw == 0 && lane < 8)
+        HA(xyz_out)[gf * HA(xyz_ld) + lane] = lane == 0 ? ctr.x : lane == 1 ? ctr.y : lane == 2 ? ctr.z : 0.f;
     if constexpr (F16) {
         // Range record of the output (ev2hands_hip.h "Range records"): amax[b] = max over the window's groups.  One device-scope
         // atomicMax per GROUP put 512 read-modify-writes on one address per window and launch; across the 8 XCDs these are
@@ -1241,19 +914,7 @@ __global__ __launch_bounds__(SAB_THREADS, (sab_min_waves<C1, C2, C3, NS, RES, MO
                     if (am > old) atomicMax(&HA(out_amax)[b], am);
                 }
             } else {
-                int* sb = reinterpret_cast<int*>(rec);
-                unsigned* sa = reinterpret_cast<unsigned*>(rec + 32);
-                if (lane == 0) { sb[wave] = (valid && am) ? b : -1; sa[wave] = am; }
-                __syncthreads();
-                if (lane == 0 && valid && am) {
-                    bool first = true;
-                    unsigned m = am;
-#pragma unroll
-                    for (int w = 0; w < WV; ++w) {
-                        if (sb[w] == b) { first = first && w >= wave; m = max(m, sa[w]); }
-                    }
-                    if (first) atomicMax(&HA(out_amax)[b], m);
-                }
+                sab_record_combine(rec, wave, lane, valid, b, am, HA(out_amax));
             }
         }
     }
@@ -1351,26 +1012,6 @@ extern "C" int ev2h_sab_timeline_read(long long* host) {
     return (int)hipMemcpyFromSymbol(host, HIP_SYMBOL(g_sab_timeline), sizeof(long long) * 256);
 }
 #endif
-template <int C1, int C2, int C3, int NS, int MODE>
-static int launch_fp(SaBP p, hipStream_t st) {
-    using Cfg = SaBCfg<C1, C2, C3, NS>;
-    auto k = sa_mlp_max_bf16_kernel<C1, C2, C3, NS, false, MODE>;
-    static PerDevice attr_set{};
-    EV2H_ONCE_PER_DEVICE(attr_set,
-        EV2H_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize, Cfg::LDS_BYTES)););
-    k<<<p.nblk, SAB_THREADS, Cfg::LDS_BYTES, st>>>(p);
-    EV2H_CHECK_LAUNCH();
-    return EV2H_OK;
-}
-
-template <int NS>
-static int dispatch_fp(const SaBP& p, const ev2h_fp_desc* d, hipStream_t st) {
-    if (d->nn_idx && d->C1 == 128 && d->C2 == 128 && d->C3 == 256) return launch_fp<128, 128, 256, NS, 1>(p, st);
-    if (!d->nn_idx && d->C1 == 256 && d->C2 == 256 && d->C3 == 32) return launch_fp<256, 256, 32, NS, 2>(p, st);
-    ev2h_set_error("ev2h_fp_mlp: unsupported chain %d-%d-%d (%s)", d->C1, d->C2, d->C3, d->nn_idx ? "interpolated" : "plain rows");
-    return EV2H_ERR_ARG;
-}
-
 // The tile-image geometry the host packer must reproduce (csrc/pack.hip: sa_images, gemm_image; tests/ref_pack.py): ONE source of
 // truth -- both assert their own numbers against this on every pack.
 int ev2h_gemm_tile_geometry(int ns, int out[2]);
@@ -1401,50 +1042,6 @@ extern "C" int ev2h_tile_geometry(int C1, int C2, int C3, int planes, int out[10
     const int rc = planes == 1 ? geometry_ns<1>(C1, C2, C3, out) : planes == 2 ? geometry_ns<2>(C1, C2, C3, out) : planes == 3 ? geometry_ns<3>(C1, C2, C3, out) : geometry_ns<4>(C1, C2, C3, out);
     if (rc) { ev2h_set_error("ev2h_tile_geometry: unsupported chain %d-%d-%d", C1, C2, C3); return rc; }
     return ev2h_gemm_tile_geometry(planes, out + 6);
-}
-
-int ev2h_fp_mlp_ex(const ev2h_fp_desc* d, int t_bf16, int out_bf16, ev2h_stream_t stream, float* row16_scale = nullptr, float w3_norm = 0.f, float b3_max = 0.f);
-extern "C" int ev2h_fp_mlp(const ev2h_fp_desc* d, ev2h_stream_t stream) { return ev2h_fp_mlp_ex(d, 0, 0, stream); }
-
-// internal (forward.hip): t_bf16 -- the input rows of form (b) are 16-bit values; out_bf16 -- the output rows are written as 16-bit
-// values.  BF16: bf16 values; F16 [r6] (with range records): fp16 values times the per-window power of two row16_scale[b] (written by the
-// out_bf16 call from the bound |W3|_1 bound(H2) + max|b3| -- w3_norm, b3_max --, read by the t_bf16 call).
-int ev2h_fp_mlp_ex(const ev2h_fp_desc* d, int t_bf16, int out_bf16, ev2h_stream_t stream, float* row16_scale, float w3_norm, float b3_max) {
-    EV2H_CHECK_ARG(d && d->T && d->W2s && d->W3s && d->b2 && d->b3 && d->out);
-    EV2H_CHECK_ARG(!(t_bf16 || out_bf16) || ((d->precision == EV2H_PREC_BF16 || (d->precision == EV2H_PREC_F16 && row16_scale && d->t_amax)) &&
-                                             (!out_bf16 || !d->out_cm) && (!t_bf16 || !d->nn_idx)));
-    EV2H_CHECK_ARG((d->nn_idx != nullptr) == (d->nn_w != nullptr));
-    EV2H_CHECK_ARG(d->B > 0 && d->N > 0 && d->ldt >= d->C1 && (d->ldt % 4) == 0);
-    const int ncols = d->out_cols > 0 ? d->out_cols : d->C3;
-    EV2H_CHECK_ARG(ncols <= d->C3 && d->ldo >= ncols);
-    if (d->nn_idx) EV2H_CHECK_ARG(d->S >= 3);
-    SaBP p{};
-    p.P1 = d->T; p.ldp = d->ldt; p.nn_idx = d->nn_idx; p.nn_w = d->nn_w; p.N = d->N;
-    p.W2s = (const char*)d->W2s; p.b2 = d->b2; p.W3s = (const char*)d->W3s; p.b3 = d->b3;
-    p.out = d->out; p.ldo = d->ldo; p.B = d->B; p.Npts = d->S; p.S = ceil_div(d->N, 32); p.K = 32;
-    p.S_total = p.S; p.s_off = 0;
-    p.ncols = ncols; p.relu_out = d->no_relu_out ? 0 : 1; p.out_cm = d->out_cm;
-    p.t_bf16 = t_bf16; p.out_bf16 = out_bf16;
-    p.row16_scale = row16_scale; p.w3_norm = w3_norm; p.b3_max = b3_max;
-    p.out_cm_stride = d->out_cm_stride ? d->out_cm_stride : (size_t)ncols * d->N;
-    p.u2 = d->w2_unscale > 0.f ? d->w2_unscale : 1.f; p.u3 = d->w3_unscale > 0.f ? d->w3_unscale : 1.f;
-    p.nblk = ceil_div(d->B * p.S, SAB_WAVES);
-    if (d->precision == EV2H_PREC_F16X2 || d->precision == EV2H_PREC_F16) {
-        p.out_amax = d->out_amax;
-        if (d->t_amax) {
-            EV2H_CHECK_ARG(d->w2_norm >= 0.f && d->b2_max >= 0.f);
-            EV2H_CHECK_ARG(d->nn_idx ? d->t_scale != nullptr : d->t_scale == nullptr);   // tables arrive scaled, plain rows do not
-            // a convex blend of table rows stays inside the table's range (+ rounding): the layer-1 bound is the input's record
-            p.p1_scale = d->t_scale; p.p1_amax = d->t_amax; p.w1x_norm = 0.f; p.dmax = 1.f; p.w2_norm = d->w2_norm; p.b2_max = d->b2_max;
-        }
-    }
-    hipStream_t st = (hipStream_t)stream;
-    if (d->precision == EV2H_PREC_BF16X3) return dispatch_fp<3>(p, d, st);
-    if (d->precision == EV2H_PREC_F16X2) return dispatch_fp<2>(p, d, st);
-    if (d->precision == EV2H_PREC_BF16) return dispatch_fp<1>(p, d, st);
-    if (d->precision == EV2H_PREC_F16) return dispatch_fp<4>(p, d, st);
-    ev2h_set_error("ev2h_fp_mlp: precision %d is not a 16-bit plane mode (F32: ev2h_three_nn_interp + ev2h_gemm)", d->precision);
-    return EV2H_ERR_ARG;
 }
 
 // called by ev2h_sa_mlp_max when d->precision != EV2H_PREC_F32

@@ -149,7 +149,7 @@ def sa_bf16_geometry(C2: int):
 
 
 def kernel_geometry(C1: int, C2: int, C3: int, ns: int) -> dict:
-    """Tile-image geometry of a chain as the KERNELS define it (ev2h_tile_geometry: csrc/sa_mlp_bf16.hip SaBCfg, csrc/gemm_bf16.hip
+    """Tile-image geometry of a chain as the KERNELS define it (ev2h_tile_geometry: csrc/sa_steps.hpp SaBCfg, csrc/gemm_bf16.hip
     GBCfg) -- the one source of truth the image builders below are asserted against."""
     out = (C.c_int * 10)()
     _lib.check(_lib.lib().ev2h_tile_geometry(C1, C2, C3, ns, out), "ev2h_tile_geometry")
@@ -157,7 +157,7 @@ def kernel_geometry(C1: int, C2: int, C3: int, ns: int) -> dict:
 
 
 def sa_bf16_images(W2: np.ndarray, W3: np.ndarray, ns: int):
-    """Byte images of the LDS weight tiles of sa_mlp_max_bf16_kernel (see SaBCfg in csrc/sa_mlp_bf16.hip).
+    """Byte images of the LDS weight tiles of sa_mlp_max_bf16_kernel and row_mlp_bf16_kernel (see SaBCfg in csrc/sa_steps.hpp).
     W2 [C2, C1], W3 [C3, C2] folded fp32 weights.  Returns (W2s, W3s, u2, u3): uint8 images of W2 / u2 and W3 / u3 and the
     power-of-two factors (plane_unscale) the kernel multiplies back."""
     u2, u3 = (chain_unscale(W2) if ns == 4 else plane_unscale(W2, ns)), plane_unscale(W3, ns)

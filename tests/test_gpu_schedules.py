@@ -30,8 +30,8 @@ SCHEDULE_THRESHOLDS = [
     ("gemm_bf16.hip", "constexpr int GO_BN = 128,", "test_gemm_small_grids_bit_identical"),
     ("gemm_bf16.hip", "if (p.nblk <= 64 && p.rowmax_rows == 0 && p.taps == 1) return launch_go_small", "test_gemm_small_grids_bit_identical"),
     ("gemm_bf16.hip", "if (p.nblk <= 128) return launch_go_pipe", "test_gemm_small_grids_bit_identical"),
-    ("sa_mlp_bf16.hip", "static constexpr int REC_SLOTS = 64;", "test_sa_range_record_past_the_window_slots"),
-    ("sa_mlp_bf16.hip", "constexpr int SAB_WAVES = 8;", "test_sa_window_counts"),
+    ("sa_steps.hpp", "static constexpr int REC_SLOTS = 64;", "test_sa_range_record_past_the_window_slots"),
+    ("sa_steps.hpp", "constexpr int SAB_WAVES = 8;", "test_sa_window_counts"),
     ("sa_mlp_bf16.hip", "(spg == 2 || spg == 4) && p.nblk < 256", "test_sa_window_counts"),
     ("points.hip", "constexpr int NN_PTS_PER_WG = 256;", "test_three_nn_across_grid_shapes"),
     ("points.hip", "ceil_div(N1, NN_PTS_PER_WG) * B < 128) ? 64 : NN_PTS_PER_WG", "test_three_nn_across_grid_shapes"),
