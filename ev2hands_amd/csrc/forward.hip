@@ -335,8 +335,8 @@ static int forward_body(const ev2h_weights* w, const ev2h_mano_consts* const* ma
     // launch and 0.26 ms of ball queries between the later ones).  There the side stream runs each quarter's ball query right behind
     // its sampling and the caller's stream launches nothing but fused kernels; the sampling is a ONE-job launch (one workgroup per CU
     // at 256 windows instead of three, on a VALU-bound kernel that everything waits for; job 0's slots of WS_FPS_STATE) -- the
-    // regressors' two samplings, which rode in the first launch, are drawn behind the last quarter, still ahead of everything that
-    // reads them (right behind quarter 0 they cost all that was won).  The queries cost the fused kernels beside them nearly what they
+    // regressors' two samplings, which rode in the first launch, are drawn later, still ahead of everything that reads them
+    // (late_selections below; right behind quarter 0 they cost all that was won).  The queries cost the fused kernels beside them nearly what they
     // took alone (the CUs' issue slots are shared: enc.sa1 stays at 2.6 ms from first to last launch while its idle time falls from
     // 0.26 to 0.02 ms); what is won is the head, 0.25 -> 0.20 ms, and the caller's stream's launches: 256 x 2048 -0.8 .. -1.3 % step
     // time on four machines, bf16 -0.8 %.
@@ -347,27 +347,51 @@ static int forward_body(const ev2h_weights* w, const ev2h_mano_consts* const* ma
     int32_t* gi1[3] = {ws.i(WS_GIDX1_0), ws.i(WS_GIDX1_1), ws.i(WS_GIDX1_2)};
     double rad1[3]; int ns1[3];
     for (int i = 0; i < 3; ++i) { rad1[i] = w->sa1.br[i].radius; ns1[i] = w->sa1.br[i].K; }
-    {
-        const int S[3] = {512, 128, 128};
-        const int64_t* init[3] = {fps_init, fps_init + 2 * (size_t)B, fps_init + 3 * (size_t)B};
-        int32_t* idx[3] = {ws.i(WS_FPS1), ws.i(WS_FPSM_L), ws.i(WS_FPSM_R)};
-        float* ctr[3] = {ws.f(WS_CTR1), ws.f(WS_CTRM_L), ws.f(WS_CTRM_R)};
-        if (!chunked) {
-            RUN(ev2h_fps_multi(ws.f(WS_PTS4), B, N, 3, S, init, idx, ctr, st));
-        } else {
-            const int q = w->sa1.npoint / FPS_CHUNKS;
-            for (int c = 0; c < FPS_CHUNKS; ++c) {          // (!side_queries: the regressors' 128-centroid samplings finish inside the first launch)
-                RUN(ev2h_fps_multi_chunk(ws.f(WS_PTS4), B, N, side_queries ? 1 : 3, S, init, idx, ctr, c * q, (c + 1) * q, ws.f(WS_FPS_STATE), sd));
-                if (side_queries) RUN(ev2h_ball_query_range(ws.f(WS_PTS4), ws.f(WS_CTR1), B, N, 512, c * q, q, 3, rad1, ns1, gi1, ws.i(WS_CNT1), sd));
-                RUN(cx.side_records(EV_SA1_QUARTER0 + c));
-            }
-            if (side_queries) RUN(ev2h_fps_multi(ws.f(WS_PTS4), B, N, 2, S + 1, init + 1, idx + 1, ctr + 1, sd));
+    const int S[3] = {512, 128, 128};
+    const int64_t* init[3] = {fps_init, fps_init + 2 * (size_t)B, fps_init + 3 * (size_t)B};
+    int32_t* idx[3] = {ws.i(WS_FPS1), ws.i(WS_FPSM_L), ws.i(WS_FPSM_R)};
+    float* ctr[3] = {ws.f(WS_CTR1), ws.f(WS_CTRM_L), ws.f(WS_CTRM_R)};
+    static const bool unfused_fp1 = getenv("EV2H_FP1_UNFUSED") != nullptr;      // A/B switch
+    const bool fp1_fused = prec != EV2H_PREC_F32 && w->fp1m.W1fs && !unfused_fp1;
+    // The selections that nobody reads before fp1 (its 3-NN) and the regressors (their samplings and ball queries), on the side stream.
+    // Where side_queries holds they are DEFERRED.  Beside the fused kernels of enc.sa1's later quarters they cost those kernels what
+    // they take alone (the <64, 96, 128> launches beside them took 409 and 503 us against 375-383 us for the other two quarters), and
+    // their readers come 3 ms and 5 ms later.  They wait for enc.sa3 (EV_ENC_SA3, recorded behind fp3's bias row) and run beside
+    // fp3, fp2 and fp1's table, the 3-NN first: it is read first, by fp1, 0.54 ms later at 256 x 2048 in f16x2.  The dense layers pay
+    // for the company as well -- fp3, fp2 and fp2's 3-NN took 150 us longer, as much as the quarters gave back (behind enc.sa2 the
+    // two wide layers of enc.sa3 did) -- so in f16x2 the step stays what it is without the deferral (11.203 against 11.200 ms),
+    // while bf16 gains 1.2 % (5.391 against 5.457 ms; behind enc.sa2: 5.412): profiles/deferred_selections_ab.txt.
+    // Same kernels, same inputs: bit-identical.
+    // (with_samplings: the regressors' samplings did not ride in enc.sa1's first sampling launch)
+    auto late_selections = [&](bool with_samplings) -> int {
+        if (fp1_fused) {
+            RUN(ev2h_three_nn_interp(ws.f(WS_PTS4), ws.f(WS_CTR1), B, N, 512, nullptr, 0, 0, nullptr, 0, ws.i(WS_NN1_IDX), ws.f(WS_NN1_W), nullptr, sd));
+            RUN(cx.side_records(EV_FP1_NN));
+        }
+        if (with_samplings) RUN(ev2h_fps_multi(ws.f(WS_PTS4), B, N, 2, S + 1, init + 1, idx + 1, ctr + 1, sd));
+        for (int h = 0; h < 2; ++h) {
+            const ev2h_sa_module& m = w->mano_sa1[h];
+            double rad[2]; int ns[2];
+            int32_t* gi[2] = {ws.i(hand(WS_GIDXM0_L, h)), ws.i(hand(WS_GIDXM1_L, h))};
+            for (int i = 0; i < 2; ++i) { rad[i] = m.br[i].radius; ns[i] = m.br[i].K; }
+            RUN(ev2h_ball_query(ws.f(WS_PTS4), ws.f(hand(WS_CTRM_L, h)), B, N, 128, 2, rad, ns, gi, ws.i(hand(WS_CNTM_L, h)), sd));
+        }
+        return cx.side_records(EV_HAND_QUERIES);
+    };
+    if (!chunked) {
+        RUN(ev2h_fps_multi(ws.f(WS_PTS4), B, N, 3, S, init, idx, ctr, st));
+    } else {
+        const int q = w->sa1.npoint / FPS_CHUNKS;
+        for (int c = 0; c < FPS_CHUNKS; ++c) {          // (!side_queries: the regressors' 128-centroid samplings finish inside the first launch)
+            RUN(ev2h_fps_multi_chunk(ws.f(WS_PTS4), B, N, side_queries ? 1 : 3, S, init, idx, ctr, c * q, (c + 1) * q, ws.f(WS_FPS_STATE), sd));
+            if (side_queries) RUN(ev2h_ball_query_range(ws.f(WS_PTS4), ws.f(WS_CTR1), B, N, 512, c * q, q, 3, rad1, ns1, gi1, ws.i(WS_CNT1), sd));
+            RUN(cx.side_records(EV_SA1_QUARTER0 + c));
         }
     }
     // fork 1: everything that needs only COORDINATES runs on the side stream, under the MFMA-bound set-abstraction kernels of
     // enc.sa1 on the caller's stream (it used to sit between them on the critical path): the sampling and the ball query of
     // enc.sa2 (its input points are enc.sa1's centroids), the 3-NN selection of fp1 (raw cloud against those centroids), then
-    // both hands' ball queries.  Same kernels, same inputs: bit-identical.
+    // both hands' ball queries (late_selections; side_queries: only enc.sa2's here).  Same kernels, same inputs: bit-identical.
     if (!chunked) RUN(cx.signal_side(EV_SAMPLED));            // (chunked: the sampling itself ran on the side stream)
     int32_t* gi2[2] = {ws.i(WS_GIDX2_0), ws.i(WS_GIDX2_1)};
     {
@@ -378,20 +402,7 @@ static int forward_body(const ev2h_weights* w, const ev2h_mano_consts* const* ma
         RUN(ev2h_ball_query(ws.f(WS_CTR1), ws.f(WS_CTR2), B, 512, 128, 2, rad, ns, gi2, ws.i(WS_CNT2), sd));
         RUN(cx.side_records(EV_SA2_QUERY));
     }
-    static const bool unfused_fp1 = getenv("EV2H_FP1_UNFUSED") != nullptr;      // A/B switch
-    const bool fp1_fused = prec != EV2H_PREC_F32 && w->fp1m.W1fs && !unfused_fp1;
-    if (fp1_fused) {
-        RUN(ev2h_three_nn_interp(ws.f(WS_PTS4), ws.f(WS_CTR1), B, N, 512, nullptr, 0, 0, nullptr, 0, ws.i(WS_NN1_IDX), ws.f(WS_NN1_W), nullptr, sd));
-        RUN(cx.side_records(EV_FP1_NN));
-    }
-    for (int h = 0; h < 2; ++h) {
-        const ev2h_sa_module& m = w->mano_sa1[h];
-        double rad[2]; int ns[2];
-        int32_t* gi[2] = {ws.i(hand(WS_GIDXM0_L, h)), ws.i(hand(WS_GIDXM1_L, h))};
-        for (int i = 0; i < 2; ++i) { rad[i] = m.br[i].radius; ns[i] = m.br[i].K; }
-        RUN(ev2h_ball_query(ws.f(WS_PTS4), ws.f(hand(WS_CTRM_L, h)), B, N, 128, 2, rad, ns, gi, ws.i(hand(WS_CNTM_L, h)), sd));
-    }
-    RUN(cx.side_records(EV_HAND_QUERIES));
+    if (!side_queries) RUN(late_selections(false));        // (side_queries: deferred, behind enc.sa3 below)
     // ---- enc.sa1 (TEHNet.py:179)
     {
         const ev2h_sa_module& m = w->sa1;
@@ -424,6 +435,10 @@ static int forward_body(const ev2h_weights* w, const ev2h_mano_consts* const* ma
     RUN(dense(cx, w->sa3[2], ws.f(WS_SA3H2), 512, B * 128, ws.f(WS_L3), 1024, 1, st, rg(R_SA3H2, 128, R_L3, 1), {.rowmax_rows = 128}));
     // ---- fp3 (TEHNet.py:184): the single l3 point is broadcast, so its 1024 inputs collapse to a per-window bias
     RUN(dense(cx, w->fp3_bcast, ws.f(WS_L3), 1024, B, ws.f(WS_FP3BIAS), 256, 0, st, rg(R_L3, 1), {.skinny = 1}));
+    if (side_queries) {         // the deferred selections: on the side stream, which has got as far as EV_SA2_QUERY, from here on
+        RUN(cx.signal_side(EV_ENC_SA3));
+        RUN(late_selections(true));
+    }
     RUN(dense(cx, w->fp3_skip, ws.f(WS_L2BUF), 520, B * 128, ws.f(WS_FP3H), 256, 1, st, rg(R_L2, 128, R_FP3H, 128, R_FEAT),
               {.group_bias = ws.f(WS_FP3BIAS), .group_rows = 128, .ldbias = 256}));
     RUN(dense(cx, w->fp3_1, ws.f(WS_FP3H), 256, B * 128, ws.f(WS_FP3O), 256, 1, st, rg(R_FP3H, 128, R_FP3O, 128)));

@@ -208,21 +208,30 @@ __global__ __launch_bounds__(256) void ball_query_kernel(const float4* __restric
     const float4* src = pts4 + (size_t)b * N;
     (void)tid;
     const int s_begin = a.s_off + (L - b * a.nchunk) * a.cpw;
-    for (int s = s_begin + wave; s < s_begin + a.cpw && s < a.s_off + a.s_cnt; s += 4) {
+    // The kernel is VALU-issue bound (its loads hit L2, its bookkeeping is scalar), so what counts is the vector instructions per
+    // 64-point chunk and radius: ONE compare where the chunk has no point in range, five more (two v_mbcnt seeded with the count,
+    // the slot test, the byte offset, the store) where it has.  For that the centroid index is made wave-uniform for the compiler as
+    // well (the centroid, the three row bases and the counts live in scalar registers, loads and stores take base + 32-bit offset),
+    // the compare's lane mask is the ballot, and only a step that crosses the end of the window tests p < N (TAIL).
+    const int wave_u = __builtin_amdgcn_readfirstlane(wave);
+    for (int s = s_begin + wave_u; s < s_begin + a.cpw && s < a.s_off + a.s_cnt; s += 4) {
         const float4 c = ctr4[(size_t)b * S + s];
         int cnt[3] = {0, 0, 0};
         int first[3] = {0, 0, 0};
-        int32_t* gbase[3];
+        char* gbase[3];
 #pragma unroll
-        for (int i = 0; i < 3; ++i) gbase[i] = (i < a.nrad) ? a.gidx[i] + ((size_t)b * S + s) * a.K[i] : nullptr;
-        // BALL_UNR chunks of 64 points per step: the distance evaluations and LDS reads of a step are independent, the
+        for (int i = 0; i < 3; ++i) gbase[i] = (i < a.nrad) ? reinterpret_cast<char*>(a.gidx[i] + ((size_t)b * S + s) * a.K[i]) : nullptr;
+        // BALL_UNR chunks of 64 points per step: the distance evaluations and loads of a step are independent, the
         // scalar bookkeeping (counts, exit test) is paid once per step; slots are still filled in ascending point order
-        for (int base = 0; base < N; base += 64 * BALL_UNR) {
+        // returns: every radius has its K neighbours
+        auto step = [&](int base, auto tail) -> bool {
+            constexpr bool TAIL = decltype(tail)::value;
             float d[BALL_UNR];
 #pragma unroll
             for (int u = 0; u < BALL_UNR; ++u) {
                 const int p = base + 64 * u + lane;
-                const float4 q = src[p < N ? p : N - 1];
+                const unsigned off = (unsigned)(TAIL ? (p < N ? p : N - 1) : p) * (unsigned)sizeof(float4);
+                const float4 q = *reinterpret_cast<const float4*>(reinterpret_cast<const char*>(src) + off);
                 // square_distance (pointnet2_utils.py:37-39): -2*(c.q) + |c|^2 + |q|^2, dot as an fma chain
                 const float dot = __fmaf_rn(c.z, q.z, __fmaf_rn(c.y, q.y, __fmul_rn(c.x, q.x)));
                 d[u] = __fadd_rn(__fadd_rn(__fmul_rn(-2.f, dot), c.w), q.w);
@@ -234,17 +243,23 @@ __global__ __launch_bounds__(256) void ball_query_kernel(const float4* __restric
 #pragma unroll
                     for (int u = 0; u < BALL_UNR; ++u) {
                         const int p = base + 64 * u + lane;
-                        const bool in = (p < N) && !(d[u] > a.r2[i]);
-                        const unsigned long long m = __ballot(in);
-                        if (cnt[i] == 0 && m != 0ull) first[i] = base + 64 * u + __ffsll((long long)m) - 1;
-                        // slot = neighbours found so far + set bits below this lane (v_mbcnt)
-                        const int pos = cnt[i] + (int)__builtin_amdgcn_mbcnt_hi((unsigned)(m >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)m, 0u));
-                        if (in && pos < a.K[i]) gbase[i][pos] = p;
-                        cnt[i] += __popcll(m);
+                        const bool in = (!TAIL || p < N) && !(d[u] > a.r2[i]);
+                        const unsigned long long m = __builtin_amdgcn_ballot_w64(in);
+                        if (m != 0ull) {                   // wave-uniform: a chunk without a hit costs its compare
+                            if (cnt[i] == 0) first[i] = base + 64 * u + __ffsll((long long)m) - 1;
+                            // slot = neighbours found so far + set bits below this lane (v_mbcnt, seeded with the count)
+                            const int pos = (int)__builtin_amdgcn_mbcnt_hi((unsigned)(m >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)m, (unsigned)cnt[i]));
+                            if (in && pos < a.K[i]) *reinterpret_cast<int32_t*>(gbase[i] + (unsigned)pos * 4u) = p;
+                            cnt[i] += __popcll(m);
+                        }
                     }
                     done = done && (cnt[i] >= a.K[i]);
                 }
             }
+            return done;
+        };
+        for (int base = 0; base < N; base += 64 * BALL_UNR) {
+            const bool done = (base + 64 * BALL_UNR <= N) ? step(base, std::false_type{}) : step(base, std::true_type{});
             if (done) break;
         }
 #pragma unroll

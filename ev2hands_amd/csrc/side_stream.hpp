@@ -17,12 +17,15 @@ enum SideEvent {
     EV_LOGITS,              // side -> caller: logits written (fused query convolution, attention)
     EV_SA2_QUERY,           // side -> caller: enc.sa2's sampling + ball query done
     EV_FP1_NN,              // side -> caller: fp1's 3-NN selection done
+    // caller -> side: enc.sa3 done and fp3's bias row written (forward.hip: side_queries) -- the selections nobody reads before fp1
+    // and the regressors wait for it, so that they run beside fp3 / fp2 and not beside the fused set-abstraction kernels
+    EV_ENC_SA3,
     // side -> caller, + c: quarter c of enc.sa1's centroids drawn (chunked path) -- and, where the side stream runs the ball queries
     // (forward.hip: side_queries), their neighbours found.  Such a query writes centroid range c of WS_GIDX1_* / WS_CNT1 while the
     // caller's stream still reads the ranges of earlier quarters: the ranges are disjoint (ev2h_ball_query_range's s_off / s_cnt,
     // ev2h_sa_desc.s_off), so only this edge orders them.
     EV_SA1_QUARTER0,
-    EV_COUNT = 14
+    EV_COUNT = 15
 };
 static_assert(EV_SA1_QUARTER0 + FPS_CHUNKS == EV_COUNT, "one event per chunk of enc.sa1's sampling");
 
