@@ -99,7 +99,7 @@ class CollisionLoss:
     """Value of the reference's intersection-aware loss term (/root/reference/src/Ev2Hands/losses.py:60-102) for a batch of
     predictions: colliding triangle pairs of the concatenated two-hand mesh in METRES (max_collisions = 16 per triangle), their
     conic distance-field penetration penalty (sigma = 0.5), mean over the windows with a non-zero penalty, times
-    collision_weight = 100.  Forward value only (the path is inference); parity unpinned (un-vendored torch-mesh-isect).
+    collision_weight = 100.  `per_window_backward` gives its gradient with respect to the vertices; parity unpinned (un-vendored torch-mesh-isect).
 
     Deviation from upstream for B > 1 (documented): losses.py:88-93 builds the triangles with
     `verts_tensor.view([-1, 3])[face_tensor]` WITHOUT offsetting the face indices per batch item, so every item indexes item 0's
@@ -114,7 +114,7 @@ class CollisionLoss:
         self.max_collisions, self.sigma, self.collision_weight, self.max_pairs = max_collisions, sigma, collision_weight, max_pairs
         self.reference_batch_quirk = reference_batch_quirk
         self._faces_key, self._faces_dev = None, None
-        self.last_counts = None
+        self.last_counts = self.last_pairs = None
 
     def _device_faces(self, fl, fr, dev):
         """the two face tables on the device, converted once per (object, device)"""
@@ -123,6 +123,11 @@ class CollisionLoss:
             self._faces_dev = (device_faces(fl, dev), device_faces(fr, dev), fl, fr)       # (the originals are kept: ids stay unique)
             self._faces_key = key
         return self._faces_dev[0], self._faces_dev[1]
+
+    @staticmethod
+    def _vertex_key(vl, vr):
+        """identifies the vertex tensors a pair search ran on (storage and version: an in-place change makes it stale)"""
+        return (vl.data_ptr(), vl._version, tuple(vl.shape), vr.data_ptr(), vr._version)
 
     def capacity(self, nf: int) -> int:
         if self.max_pairs is not None:
@@ -145,6 +150,7 @@ class CollisionLoss:
         tensors prepared once).  work: optional buffers of `workspace()` (B at most theirs): the result is a view of work['loss']."""
         vl, vr = outs["left"]["vertices"], outs["right"]["vertices"]
         dev = vl.device
+        self._pairs_key = self._vertex_key(vl, vr)
         if work is not None:
             b = vl.shape[0]
             wl, wr = work["verts"][0][:b], work["verts"][1][:b]
@@ -164,13 +170,47 @@ class CollisionLoss:
         else:
             counts, pairs = mesh_collisions(vl, vr, flt, frt, max_pairs=cap, scale=1.0, max_per_triangle=self.max_collisions)
             loss = torch.zeros(B, device=dev, dtype=torch.float64)
-        self.last_counts = counts
+        self.last_counts, self.last_pairs = counts, pairs
         vlc, vrc = vl.to(torch.float32).contiguous(), vr.to(dev, torch.float32).contiguous()
         _lib.check(_lib.lib().ev2h_collision_penalty(vlc.data_ptr(), vrc.data_ptr(),
                                                      flt.data_ptr(), frt.data_ptr(), B, nv, flt.shape[0], 1.0, float(self.sigma),
                                                      pairs.data_ptr(), counts.data_ptr(), cap, loss.data_ptr(),
                                                      _lib.stream_handle()), "ev2h_collision_penalty")
         return loss
+
+    def window_coefficients(self, penalties: torch.Tensor, upstream=1.0) -> torch.Tensor:
+        """d(upstream * loss) / d(per-window penalty), [B] float64 on the device, no host read: the loss is the mean over the windows
+        with a non-zero penalty times collision_weight, so upstream * collision_weight / n_nonzero for those windows and 0 elsewhere."""
+        nz = penalties != 0
+        up = upstream.to(penalties.device, torch.float64) if torch.is_tensor(upstream) else float(upstream)
+        return torch.where(nz, up * self.collision_weight / nz.sum().clamp(min=1).to(torch.float64), torch.zeros_like(penalties))
+
+    def per_window_backward(self, outs, coef, faces=None, work=None) -> torch.Tensor:
+        """ev2h_collision_penalty_backward: [B, 2, nv, 3] float64 = coef[b] * d penalty[b] / d vertex (left hand, then right) for the
+        meshes of `outs`, over the pair list of the search per_window() ran on the same `outs` last (the list is a constant of the
+        derivative, as upstream's search under torch.no_grad()); without such a search one is run.  coef: [B] float64 on the device
+        (window_coefficients).  work: optional dict with a 'g_verts' [>= B, 2, nv, 3] float64 buffer to write into."""
+        if self.reference_batch_quirk:
+            raise NotImplementedError("the upstream batch quirk (every window reads window 0's vertices) has no backward here")
+        vl, vr = outs["left"]["vertices"], outs["right"]["vertices"]
+        dev = vl.device
+        B, nv, _ = vl.shape
+        fl, fr = faces if faces is not None else (outs["left"]["faces"], outs["right"]["faces"])
+        flt, frt = self._device_faces(fl, fr, dev)
+        cap = self.capacity(flt.shape[0])
+        if self.last_pairs is None or getattr(self, "_pairs_key", None) != self._vertex_key(vl, vr) or tuple(self.last_pairs.shape) != (B, cap, 2):
+            self.per_window(outs, faces)
+        _lib._dev_tensor(coef, "coef", torch.float64, (B,), dev)
+        if work is not None and work.get("g_verts") is not None:
+            g = work["g_verts"][:B]
+        else:
+            g = torch.empty(B, 2, nv, 3, device=dev, dtype=torch.float64)
+        _lib._dev_tensor(g, "g_verts", torch.float64, (B, 2, nv, 3), dev)
+        vlc, vrc = vl.detach().to(torch.float32).contiguous(), vr.detach().to(dev, torch.float32).contiguous()
+        _lib.check(_lib.lib().ev2h_collision_penalty_backward(vlc.data_ptr(), vrc.data_ptr(), flt.data_ptr(), frt.data_ptr(), B, nv, flt.shape[0], 1.0,
+                                                              float(self.sigma), self.last_pairs.data_ptr(), self.last_counts.data_ptr(), cap,
+                                                              coef.data_ptr(), g.data_ptr(), _lib.stream_handle()), "ev2h_collision_penalty_backward")
+        return g
 
     def truncated(self) -> bool:
         """True if the last per_window() found more pairs in some window than its pair list holds (host synchronisation)."""

@@ -18,6 +18,25 @@ import torch
 from . import _lib, synth
 
 
+PACKED_NAMES = ("hands_mean", "comps", "blend_T", "v_template", "J_template", "J_shape", "weights")
+
+
+def packed_arrays(assets: dict, shapedirs: np.ndarray, ncomps: int) -> dict:
+    """The float32 constants of ev2h_mano_consts as contiguous host arrays (the layouts of include/ev2hands_hip.h): what both
+    ev2h_mano and ev2h_mano_backward compute from.  assets: float64 arrays; shapedirs: the (possibly sign-fixed) [778, 3, 10]."""
+    sd = np.asarray(shapedirs, dtype=np.float64)
+    blend = np.zeros((145, 2336), dtype=np.float64)
+    blend[:10, :2334] = sd.reshape(2334, 10).T
+    blend[10:, :2334] = np.asarray(assets["posedirs"], dtype=np.float64).reshape(2334, 135).T
+    jr = np.asarray(assets["J_regressor"], dtype=np.float64)
+    vt = np.asarray(assets["v_template"], dtype=np.float64)
+    out = {"hands_mean": assets["hands_mean"], "comps": np.asarray(assets["hands_components"])[:ncomps], "blend_T": blend,
+           "v_template": vt.reshape(-1), "J_template": (jr @ vt).reshape(-1),                     # [16,3]
+           "J_shape": np.einsum("jv,vck->kjc", jr, sd).reshape(10, 48),                           # [10][j*3+c]
+           "weights": assets["weights"]}
+    return {k: np.ascontiguousarray(np.asarray(v, dtype=np.float32)) for k, v in out.items()}
+
+
 class ManoOutput:
     def __init__(self, vertices, joints):
         self.vertices = vertices
@@ -60,30 +79,17 @@ class ManoHand:
         ver = self.shapedirs._version
         if self._consts is not None and self._packed_version == ver:
             return self._consts
-        a = self._assets
-        sd = self.shapedirs.detach().cpu().double().numpy()
-        pdirs = a["posedirs"]
-        blend = np.zeros((145, 2336), dtype=np.float64)
-        blend[:10, :2334] = sd.reshape(2334, 10).T
-        blend[10:, :2334] = pdirs.reshape(2334, 135).T
-        jr = a["J_regressor"]
-        J_t = jr @ a["v_template"]                                  # [16,3]
-        J_s = np.einsum("jv,vck->kjc", jr, sd).reshape(10, 48)     # [10][j*3+c]
+        arrays = packed_arrays(self._assets, self.shapedirs.detach().cpu().double().numpy(), self.ncomps)
         keep = []
 
         def dev(x):
-            tt = torch.from_numpy(np.ascontiguousarray(np.asarray(x, dtype=np.float32))).to(self.device)
+            tt = torch.from_numpy(x).to(self.device)
             keep.append(tt)
             return tt.data_ptr()
 
         c = _lib.ManoConsts()
-        c.hands_mean = dev(a["hands_mean"])
-        c.comps = dev(a["hands_components"][:self.ncomps])
-        c.blend_T = dev(blend)
-        c.v_template = dev(a["v_template"].reshape(-1))
-        c.J_template = dev(J_t.reshape(-1))
-        c.J_shape = dev(J_s)
-        c.weights = dev(a["weights"])
+        for name in PACKED_NAMES:
+            setattr(c, name, dev(arrays[name]))
         for i, v in enumerate(synth.MANO_TIPS[self.side]):
             c.tips[i] = v
         c.ncomps = self.ncomps
@@ -93,8 +99,7 @@ class ManoHand:
         return c
 
     # -- reference adapter interface -------------------------------------------------------------
-    def __call__(self, global_orient, hand_pose, betas, transl):
-        prm = torch.cat([global_orient, hand_pose, betas, transl], 1).to(self.device, torch.float32).contiguous()
+    def _forward(self, prm):
         B = prm.shape[0]
         verts = torch.empty(B, 778, 3, device=self.device, dtype=torch.float32)
         joints = torch.empty(B, 21, 3, device=self.device, dtype=torch.float32)
@@ -102,7 +107,77 @@ class ManoHand:
         L = _lib.lib()
         _lib.check(L.ev2h_mano(C.byref(c), prm.data_ptr(), prm.shape[1], B, verts.data_ptr(), 0, joints.data_ptr(), 0,
                                _lib.stream_handle()), "ev2h_mano")
-        return ManoOutput(verts, joints)
+        return verts, joints
+
+    def __call__(self, global_orient, hand_pose, betas, transl):
+        parts = (global_orient, hand_pose, betas, transl)
+        if torch.is_grad_enabled() and any(t.requires_grad for t in parts):
+            # differentiable: the same kernel forward, ev2h_mano_backward behind it (a float32 input gets its gradient rounded once)
+            verts, joints = _ManoFunction.apply(self, *parts)
+            return ManoOutput(verts, joints)
+        prm = torch.cat(parts, 1).to(self.device, torch.float32).contiguous()
+        return ManoOutput(*self._forward(prm))
+
+    def vjp(self, params, grad_vertices=None, grad_joints=None, out=None, accumulate: bool = False):
+        """ev2h_mano_backward: params float32 [B, 16 + ncomps] (rows global_orient | hand_pose | betas | transl, dense or a view with
+        dense rows), grad_vertices [B, 778, 3] and / or grad_joints [B, 21, 3] (the gradients of what __call__ returns; converted to
+        float64 unless they are float64 with dense windows) -> float64 [B, 16 + ncomps], the gradient of the parameter rows.  `out`: a
+        float64 [B, 16 + ncomps] tensor with dense rows to write, or with accumulate=True to add onto.  No host synchronisation."""
+        P = 16 + self.ncomps
+        if not isinstance(params, torch.Tensor) or params.dim() != 2 or params.shape[0] < 1:
+            raise ValueError(f"params must be a float32 [B, {P}] CUDA tensor with B >= 1")
+        B = int(params.shape[0])
+        _lib._dev_tensor(params, "params", torch.float32, (B, P), self.device, contiguous=False)
+        if params.stride(1) != 1 or (B > 1 and params.stride(0) < P):
+            raise ValueError(f"params: rows must be dense and must not overlap, got strides {params.stride()}")
+        if grad_vertices is None and grad_joints is None:
+            raise ValueError("one of grad_vertices and grad_joints is needed")
+        g, gs = [], []
+        for t, name, shape in ((grad_vertices, "grad_vertices", (B, 778, 3)), (grad_joints, "grad_joints", (B, 21, 3))):
+            stride = 0
+            if t is not None:
+                if not isinstance(t, torch.Tensor) or tuple(t.shape) != shape or t.device != self.device or not t.dtype.is_floating_point:
+                    raise ValueError(f"{name} must be a floating-point tensor {list(shape)} on {self.device}")
+                if t.dtype != torch.float64 or t.stride()[1:] != (3, 1) or (B > 1 and t.stride(0) < shape[1] * 3):
+                    t = t.to(torch.float64).contiguous()                  # (a float64 view with dense windows is read in place)
+                stride = int(t.stride(0)) if B > 1 else 0
+            g.append(t)
+            gs.append(stride)
+        if out is None:
+            if accumulate:
+                raise ValueError("accumulate=True needs `out`")
+            out = torch.empty(B, P, device=self.device, dtype=torch.float64)
+        _lib._dev_tensor(out, "out", torch.float64, (B, P), self.device, contiguous=False)
+        if out.stride(1) != 1 or (B > 1 and out.stride(0) < P):
+            raise ValueError(f"out: rows must be dense and must not overlap, got strides {out.stride()}")
+        c = self.consts()
+        _lib.check(_lib.lib().ev2h_mano_backward(C.byref(c), params.data_ptr(), int(params.stride(0)) if B > 1 else P, B, _lib.ptr(g[0]), gs[0],
+                                                 _lib.ptr(g[1]), gs[1], out.data_ptr(), int(out.stride(0)) if B > 1 else 0, 1 if accumulate else 0,
+                                                 _lib.stream_handle()), "ev2h_mano_backward")
+        return out
+
+
+class _ManoFunction(torch.autograd.Function):
+    """ManoHand.__call__ for inputs that require grad: ev2h_mano forward, ManoHand.vjp backward."""
+
+    @staticmethod
+    def forward(ctx, hand, global_orient, hand_pose, betas, transl):
+        parts = (global_orient, hand_pose, betas, transl)
+        prm = torch.cat([t.detach() for t in parts], 1).to(hand.device, torch.float32).contiguous()
+        ctx.hand, ctx.meta = hand, [(t.shape[1], t.dtype, t.device) for t in parts]
+        ctx.save_for_backward(prm)
+        return hand._forward(prm)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g_verts, g_joints):
+        (prm,) = ctx.saved_tensors
+        g = ctx.hand.vjp(prm, g_verts, g_joints)
+        grads, off = [], 0
+        for need, (n, dtype, dev) in zip(ctx.needs_input_grad[1:], ctx.meta):
+            grads.append(g[:, off:off + n].to(dev, dtype) if need else None)
+            off += n
+        return (None, *grads)
 
 
 # ------------------------------------------------------------------------------------------- assets

@@ -128,3 +128,26 @@ def segmentation_score(class_logits: torch.Tensor, labels: torch.Tensor, out=Non
     _lib.check(_lib.lib().ev2h_segmentation_score(class_logits.data_ptr(), stride, labels.data_ptr(), B, N, conf.data_ptr(), num.data_ptr(),
                                                   den.data_ptr(), ignored.data_ptr(), _lib.stream_handle()), "ev2h_segmentation_score")
     return conf, num, den, ignored
+
+
+def segmentation_score_backward(class_logits: torch.Tensor, labels: torch.Tensor, scale: torch.Tensor, out=None) -> torch.Tensor:
+    """ev2h_segmentation_score_backward: the gradient of the weighted cross-entropy of losses.py:203 with respect to the logits.
+    class_logits, labels as segmentation_score takes them; scale: float64 0-dim (or [1]) tensor on the device, upstream / sum(ce_den).
+    -> float32 [B, 4, N] = scale * w_y * (softmax - onehot) at the labelled points, 0 at label 0 and at labels outside 0..3 (an
+    all-ignored batch gives zeros whatever `scale` is).  `out`: a contiguous float32 [B, 4, N] tensor to write.  No host synchronisation."""
+    if not isinstance(class_logits, torch.Tensor) or class_logits.dim() != 3 or class_logits.shape[0] < 1 or class_logits.shape[2] < 1:
+        raise ValueError("class_logits must be a float32 [B, 4, N] CUDA tensor with B, N >= 1")
+    B, N, dev = int(class_logits.shape[0]), int(class_logits.shape[2]), class_logits.device
+    _dev_tensor(class_logits, "class_logits", torch.float32, (B, 4, N), dev, contiguous=False)
+    if class_logits.stride()[1:] != (N, 1) or (B > 1 and class_logits.stride(0) < 4 * N):
+        raise ValueError(f"class_logits: each window's [4, N] block must be dense and the windows must not overlap, got strides {class_logits.stride()}")
+    stride = int(class_logits.stride(0)) if B > 1 else 4 * N
+    _dev_tensor(labels, "labels", torch.int64, (B, N), dev)
+    if not isinstance(scale, torch.Tensor) or scale.dtype != torch.float64 or scale.numel() != 1 or scale.device != dev:
+        raise ValueError("scale must be a float64 tensor of one element on the logits' device")
+    if out is None:
+        out = torch.empty(B, 4, N, device=dev, dtype=torch.float32)
+    _dev_tensor(out, "out", torch.float32, (B, 4, N), dev)
+    _lib.check(_lib.lib().ev2h_segmentation_score_backward(class_logits.data_ptr(), stride, labels.data_ptr(), B, N, scale.data_ptr(), out.data_ptr(), 0,
+                                                           _lib.stream_handle()), "ev2h_segmentation_score_backward")
+    return out

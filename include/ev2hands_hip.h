@@ -379,6 +379,19 @@ int ev2h_mano(const ev2h_mano_consts* c, const float* params, int ldp, int B, fl
  * axis-angle -> matrix by the formula of losses.py:14-51: quaternion route, theta + 1e-8 inside the norm).  Only hands_mean, comps
  * and ncomps of `c` are used. */
 int ev2h_mano_rotations(const ev2h_mano_consts* c, const float* params, int ldp, int B, float* rot, ev2h_stream_t stream);
+/* The vector-Jacobian product of ev2h_mano (csrc/loss_grad.hip): g_params [B][16 + ncomps] float64, window b at + b * g_params_stride
+ * doubles (0 = dense), = sum over the outputs of (gradient of the output) * d(output) / d(params row), for the gradients
+ * g_verts [B][778][3] and g_joints [B][21][3] float64 (window b at + b * stride doubles, 0 = 2334 / 63; either may be NULL = zeros,
+ * not both).  accumulate != 0 adds onto what g_params holds, else it is overwritten.  Only the 16 + ncomps values of a row are touched.
+ * Arithmetic: the forward chain is recomputed in float64 from the float32 parameters and constants (the formulas of ev2h_mano,
+ * theta + 1e-8 inside the norm; the final `* 1000 / 1000` has derivative 1) and differentiated in float64.  One workgroup per
+ * window, every sum in a fixed order and no atomics: the same call gives the same bytes, and window b's row depends on window b's
+ * inputs only, whatever the batch.
+ * EV2H_ERR_ARG, before any device call: a null c / params / g_params / constant, both gradients NULL, B < 1, ncomps outside 1..45,
+ * ldp < 16 + ncomps, a stride below its row, a fingertip vertex outside 0..777.  One launch, no host synchronisation, capturable. */
+int ev2h_mano_backward(const ev2h_mano_consts* c, const float* params, int ldp, int B, const double* g_verts, size_t g_verts_stride,
+                       const double* g_joints, size_t g_joints_stride, double* g_params, size_t g_params_stride, int accumulate,
+                       ev2h_stream_t stream);
 
 /* ---- event window -> [5, N] tensor (next row 8f-1; dataset/evaluation_stream.py:187-225, ev2hands_r.py:108-159, erpc.py:169-249) ---- */
 /* Per-pixel accumulation + np.nonzero-order compaction of B ragged windows.  events: device float64 rows of ev_stride (>= 4)
@@ -657,6 +670,16 @@ int ev2h_joint_metrics_f32_frames(const float* j3d_left, const float* j3d_right,
  * without such a point has 0 and 0); ignored [B] = points whose label lies outside 0..3, which are counted nowhere else. */
 int ev2h_segmentation_score(const float* class_logits, size_t logits_stride, const int64_t* labels, int B, int N, int32_t* confusion,
                             double* ce_num, double* ce_den, int32_t* ignored, ev2h_stream_t stream);
+/* The gradient of that weighted cross-entropy with respect to the logits (csrc/loss_grad.hip):
+ *   g_logits[b][c][n] = *scale * w_y * (softmax_c(x) - [c == y])   for a label y in 1..3 (w = [1, 30, 30, 10]),
+ *   0 for label 0 and for labels outside 0..3 (written as 0, not as *scale * 0: a batch without a labelled point, whose mean is
+ *   0 / 0, has an all-zero gradient whatever *scale is, as torch's F.cross_entropy gives).
+ * scale: DEVICE float64 scalar, the caller's upstream / sum(ce_den).  The softmax is evaluated in float64 and the product rounded to
+ * float32 once.  class_logits / logits_stride as in ev2h_segmentation_score; g_logits [B][4][N] float32, window b at
+ * + b * g_logits_stride floats (0 = 4 * N).  N any positive number.  One thread per point: bitwise reproducible, and a window's
+ * output depends on that window and *scale only.  EV2H_ERR_ARG for a null pointer, B or N < 1, a stride below 4 * N. */
+int ev2h_segmentation_score_backward(const float* class_logits, size_t logits_stride, const int64_t* labels, int B, int N,
+                                     const double* scale, float* g_logits, size_t g_logits_stride, ev2h_stream_t stream);
 /* ev2h_eval_accumulate for the two scorers above.  State, zeroed before the first call except scalars = (0, -1):
  *   sums [3 * (num_steps + 1) + 2] float64: the three PCK curves summed over the windows, then ce_num and ce_den;
  *   conf_total [17] int64: the confusion matrix, then `ignored`;
@@ -723,6 +746,20 @@ int ev2h_loss_terms(const float* params_left, const float* params_right, size_t 
                     const float* target_j3d, const float* target_j2d, size_t j2d_ld, const int32_t* target_flags, int A,
                     const int32_t* index, int B, const float* projection, float width, float height, double* terms,
                     int32_t* flags, int32_t* has_gt, ev2h_stream_t stream);
+/* The backward twin of ev2h_loss_terms: the same inputs, and coef, a DEVICE pointer to [EV2H_LOSS_NT] float64 values, each
+ * d(total) / d(numerator of that slot) (ev2hands_amd.losses.term_coefficients builds them from ev2h_loss_accumulate's state).  Writes
+ * g_params [B][2][16 + n_pose] and g_j3d [B][2][21][3] float64 (dense): the partial derivatives of the total with respect to the
+ * parameter rows and to the joints as separate inputs.  Per-element derivatives are torch's, evaluated in float64 from the float32
+ * inputs: mse -> 2 (a - b); l1 -> the sign of the float32 difference exactly as the forward forms it, sign(0) = sign(NaN) = 0;
+ * mse(x, x) -> 0 (NaN for a non-finite x); mode 0: x^2 -> 2 x, and j2d through opengl_projection_transform including the division
+ * by w.  The mask is a multiplier, as in the forward.  A window whose index lies outside [0, A) gets zeros.  One wavefront per
+ * window, fixed-order sums, no atomics: bitwise reproducible, and window b's rows depend on window b's inputs and coef only.
+ * Arguments are checked as in ev2h_loss_terms (plus coef, g_params, g_j3d non-null).  One launch, no host synchronisation. */
+int ev2h_loss_terms_backward(const float* params_left, const float* params_right, size_t params_stride, const float* j3d_left,
+                             const float* j3d_right, size_t j3d_stride, int n_pose, int mode, const float* target_params,
+                             const float* target_j3d, const float* target_j2d, size_t j2d_ld, const int32_t* target_flags, int A,
+                             const int32_t* index, int B, const float* projection, float width, float height, const double* coef,
+                             double* g_params, double* g_j3d, ev2h_stream_t stream);
 /* Folds ev2h_loss_terms' outputs of B windows into a running state.  state [EV2H_LOSS_NSTATE] float64, zeroed before the first call:
  * [EV2H_LOSS_NT numerators | 3 counts (interacting, valid_left, valid_right) | collision sum, collision count | windows];  scalars
  * [2] int32, (0, -1) before the first call: windows counted, and stopped_at = the id of the first window with has_gt = 0
@@ -764,6 +801,17 @@ int ev2h_mesh_collisions_ws(const float* verts_left, const float* verts_right, c
 int ev2h_collision_penalty(const float* verts_left, const float* verts_right, const int32_t* faces_left, const int32_t* faces_right,
                            int B, int nv, int nf, float scale, double sigma, const int32_t* pairs, const int32_t* counts, int max_pairs,
                            double* loss, ev2h_stream_t stream);
+/* The gradient of that penalty (csrc/loss_grad.hip): the same meshes, pairs, counts, max_pairs, scale and sigma, and coef [B]
+ * float64 on the DEVICE;  g_verts [B][2][nv][3] float64 (left hand, then right) = coef[b] * d loss[b] / d vertex.  The pair list is a
+ * constant (the reference searches under torch.no_grad()).  Every pair's cone terms are differentiated with respect to all six
+ * vertices -- circumcentre, circumradius and normal of the receiving face, and the three intruding points -- in forward mode over
+ * the forward's own formulas; the forward's branches (degenerate face, point in front of the face, point outside the cone) select
+ * zero.  One workgroup per window, contributions added per vertex in pair order, no atomics: bitwise reproducible, and window b's
+ * output depends on window b only.  A window without pairs gives zeros; of a window whose count exceeds max_pairs the listed pairs
+ * are used.  EV2H_ERR_ARG: a null pointer, B < 1, nv outside 3..778, nf outside 1..1538, max_pairs < 1, sigma <= 0. */
+int ev2h_collision_penalty_backward(const float* verts_left, const float* verts_right, const int32_t* faces_left,
+                                    const int32_t* faces_right, int B, int nv, int nf, float scale, double sigma, const int32_t* pairs,
+                                    const int32_t* counts, int max_pairs, const double* coef, double* g_verts, ev2h_stream_t stream);
 
 /* ---- demo frames: event, segmentation and mesh panels (demo.py:18-68,113-146; dataset/ev2hands_r.py:148-156) -------------- */
 /* What the reference's demo item calls 'coordinates' (ev2hands_r.py:149-154) and the two counts its event_frame is coloured
