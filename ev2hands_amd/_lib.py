@@ -99,7 +99,7 @@ W_EQUALIZED, W_UNEQUALIZED_OK = 1, 2
 # ev2h_joint_metrics_f32_frames, ev2h_segmentation_score, ev2h_eval_s_accumulate), and for the loss exports (ev2h_loss_terms,
 # ev2h_loss_accumulate), and for the augmented training item (ev2h_event_window_build_s_ranges_aug), and for the fine-tuning item
 # (ev2h_event_window_build_ranges_flip, ev2h_finetune_resolve, ev2h_finetune_targets), and for the gradient exports (ev2h_mano_backward,
-# ev2h_segmentation_score_backward, ev2h_loss_terms_backward, ev2h_collision_penalty_backward).
+# ev2h_segmentation_score_backward, ev2h_loss_terms_backward, ev2h_collision_penalty_backward), and for the test hooks (ev2h_dbg_*).
 ABI_VERSION = 8     # 8: EV2H_PREC_F16 (one fp16 plane with f16x2's range machinery); 3: F16X2 range records; 4: ev2h_fp_mlp, ev2h_weights.fp1m; 5: window strides of the outputs; 6: ev2h_pack_weights, ev2h_weights.flags; 7: ev2h_sa_desc.xyz_out
 
 PREC = {"f32": 0, "bf16": 1, "f16x2": 2, "bf16x3": 3, "f16": 4}
@@ -135,6 +135,8 @@ EXPORTS = [
     "ev2h_event_window_build_s_ranges_aug",
     "ev2h_event_window_build_ranges_flip", "ev2h_finetune_resolve", "ev2h_finetune_targets",
     "ev2h_mano_backward", "ev2h_segmentation_score_backward", "ev2h_loss_terms_backward", "ev2h_collision_penalty_backward",
+    # test hooks, not part of the stable interface (include/ev2hands_hip.h: "Test hooks"; ev2hands_amd/ops.py: *_rows16, dense_zsum, ...)
+    "ev2h_dbg_fp_mlp_rows16", "ev2h_dbg_gemm_zsum_supported", "ev2h_dbg_gemm_zsum", "ev2h_dbg_attn_simfold_partials", "ev2h_dbg_attn_context_rows16",
 ]
 
 _lib = None
@@ -237,6 +239,11 @@ def lib() -> C.CDLL:
     L.ev2h_collision_penalty_backward.argtypes = [vp, vp, vp, vp, ci, ci, ci, C.c_float, C.c_double, vp, vp, ci, vp, vp, vp]
     L.ev2h_mano_backward.argtypes = [C.POINTER(ManoConsts), vp, ci, ci, vp, C.c_size_t, vp, C.c_size_t, vp, C.c_size_t, ci, vp]
     L.ev2h_segmentation_score_backward.argtypes = [vp, C.c_size_t, vp, ci, ci, vp, vp, C.c_size_t, vp]
+    L.ev2h_dbg_fp_mlp_rows16.argtypes = [C.POINTER(FpDesc), ci, ci, vp, C.c_float, C.c_float, vp]
+    L.ev2h_dbg_gemm_zsum_supported.argtypes = [C.POINTER(GemmDesc)]
+    L.ev2h_dbg_gemm_zsum.argtypes = [C.POINTER(GemmDesc), vp, vp, ci, vp, vp]
+    L.ev2h_dbg_attn_simfold_partials.argtypes = [vp, ci, vp, ci, ci, vp, vp, vp, vp, vp, vp]
+    L.ev2h_dbg_attn_context_rows16.argtypes = [vp, vp, ci, ci, ci, vp, vp, ci, vp, vp, vp]
     L.ev2h_event_window_pixels.argtypes = [vp, vp, ci, vp, ci, ci, vp, vp, vp, vp]
     L.ev2h_demo_point_panels.argtypes = [vp, vp, vp, vp, C.c_size_t, ci, ci, ci, ci, vp, ci, ci, ci, vp]
     L.ev2h_render_scratch_bytes.restype = C.c_size_t

@@ -318,3 +318,14 @@ int ev2h_attn_context_f16rows(const float* sim, const void* value_pm, int ldv, i
     EV2H_CHECK_LAUNCH();
     return EV2H_OK;
 }
+
+// test hooks (include/ev2hands_hip.h: "Test hooks"): the internal entry points above as they are; vscale selects the row format
+extern "C" int ev2h_dbg_attn_simfold_partials(const float* zpart, int rows_per_partial, const float* logits_pm, int B, int N, const float* w4t_left,
+                                              const float* w4t_right, const float* b4_left, const float* b4_right, float* sim, ev2h_stream_t stream) {
+    return ev2h_attn_simfold_partials(zpart, rows_per_partial, logits_pm, B, N, w4t_left, w4t_right, b4_left, b4_right, sim, stream);
+}
+extern "C" int ev2h_dbg_attn_context_rows16(const float* sim, const void* value16, int ldv, int B, int N, float* hf8, uint32_t* hf_amax, int amax_hand_stride,
+                                            const float* value_unscale, const float* vscale, ev2h_stream_t stream) {
+    if (!vscale) return ev2h_attn_context_bf16rows(sim, value16, ldv, B, N, hf8, value_unscale, stream);
+    return ev2h_attn_context_f16rows(sim, value16, ldv, B, N, hf8, hf_amax, amax_hand_stride, value_unscale, vscale, stream);
+}

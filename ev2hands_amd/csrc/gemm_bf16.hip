@@ -900,6 +900,12 @@ int ev2h_gemm_bf16_zsum(const ev2h_gemm_desc* d, const float* key_pm, float* zpa
     return with_planes(d->precision, [&](auto ns) { return launch_go_t<ns(), true, true>(p, (const char*)d->Ws, (hipStream_t)stream); });
 }
 
+// test hooks (include/ev2hands_hip.h: "Test hooks"): the two functions above as they are
+extern "C" int ev2h_dbg_gemm_zsum_supported(const ev2h_gemm_desc* d) { return ev2h_gemm_bf16_zsum_supported(d); }
+extern "C" int ev2h_dbg_gemm_zsum(const ev2h_gemm_desc* d, const float* key_pm, float* zpart, int x_16, const float* x_scale, ev2h_stream_t stream) {
+    return ev2h_gemm_bf16_zsum(d, key_pm, zpart, x_16, stream, x_scale);
+}
+
 // called by ev2h_gemm when d->precision != EV2H_PREC_F32 (arguments already validated there)
 int ev2h_gemm_bf16(const ev2h_gemm_desc* d, ev2h_stream_t stream) {
     EV2H_CHECK_ARG((d->K % 8) == 0);

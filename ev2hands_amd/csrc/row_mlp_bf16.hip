@@ -340,3 +340,9 @@ int ev2h_fp_mlp_ex(const ev2h_fp_desc* d, int t_bf16, int out_bf16, ev2h_stream_
     ev2h_set_error("ev2h_fp_mlp: precision %d is not a 16-bit plane mode (F32: ev2h_three_nn_interp + ev2h_gemm)", d->precision);
     return EV2H_ERR_ARG;
 }
+
+// test hook (include/ev2hands_hip.h: "Test hooks"): ev2h_fp_mlp_ex as it is
+extern "C" int ev2h_dbg_fp_mlp_rows16(const ev2h_fp_desc* d, int rows_in_16, int rows_out_16, float* row16_scale, float w3_norm, float b3_max,
+                                      ev2h_stream_t stream) {
+    return ev2h_fp_mlp_ex(d, rows_in_16, rows_out_16, stream, row16_scale, w3_norm, b3_max);
+}

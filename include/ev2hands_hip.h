@@ -1045,6 +1045,37 @@ const void* ev2h_workspace_buffer(void* workspace, int B, int N, const char* nam
  * (ADVICE r5); ev2hands_amd's TEHNet.debug_buffer widens it. */
 const void* ev2h_workspace_buffer_ex(void* workspace, int B, int N, const char* name, size_t* count, int* elem_type);
 
+/* ---- Test hooks: NOT part of the stable interface ---------------------------------------------------------------------------
+ * From l0 on, ev2h_forward runs through kernels that have no operator entry point of their own: the row chains on 16-bit rows, the
+ * first query convolution whose epilogue forms the attention's key-weighted partial sums, the fold over those partials and the
+ * attention contexts on 16-bit value rows.  Each hook below forwards its arguments UNCHANGED to the internal function named and
+ * returns what it returns, so that tests/test_gpu_fused_tail.py can hold each kernel to a float64 reference on its own.  They may
+ * change or disappear with the internal functions; a product calls ev2h_forward.
+ *
+ * ev2h_dbg_fp_mlp_rows16 -> ev2h_fp_mlp_ex, csrc/row_mlp_bf16.hip: ev2h_fp_mlp with 16-bit rows.  rows_in_16: form (b) only, T holds
+ *   16-bit values (ldt counts values); rows_out_16: `out` receives 16-bit values (ldo counts values; no out_cm).  BF16: bf16 values.
+ *   F16 (needs t_amax and row16_scale): fp16 values TIMES the per-window power of two row16_scale[b] (float [B]) -- written by the
+ *   rows_out_16 call, which chooses it from the bound w3_norm * bound(H2) + b3_max (max row L1 norm of W3, max |b3|) and records the
+ *   maximum of the STORED values in out_amax; read by the rows_in_16 call, whose t_amax is the record of the stored values.
+ * ev2h_dbg_gemm_zsum_supported / ev2h_dbg_gemm_zsum -> ev2h_gemm_bf16_zsum_supported / ev2h_gemm_bf16_zsum, csrc/gemm_bf16.hip:
+ *   d describes the k = 3 GEMM as for ev2h_gemm (Y unused; Ws with 128-row tiles, K % 32 == 0, rows_per_seq % 128 == 0, N % 128 == 0,
+ *   range groups that tile); key_pm [M][4]; zpart [M / 128][12][N] receives, per 128-row tile, row c * 3 + t =
+ *   sum over the tile's rows m of y[m][:] * key[m - t + 1][c] (key zero outside m's window), y = the GEMM's output after bias, ReLU
+ *   and post affine.  x_16: X holds 16-bit values (ldx counts values): bf16 in BF16; in F16 fp16 values times x_scale[group] (float
+ *   per group of x_group_rows rows, required).
+ * ev2h_dbg_attn_simfold_partials -> ev2h_attn_simfold_partials, csrc/attention.hip: the second half of ev2h_attn_sim_folded on given
+ *   partials zpart [B][N / rows_per_partial][12][512].
+ * ev2h_dbg_attn_context_rows16 -> ev2h_attn_context_bf16rows where vscale == NULL (bf16 value rows; hf_amax is not maintained), else
+ *   ev2h_attn_context_f16rows, fp16 rows stored times vscale[b]: ev2h_attn_context on 16-bit value rows, ldv counts values. */
+int ev2h_dbg_fp_mlp_rows16(const ev2h_fp_desc* d, int rows_in_16, int rows_out_16, float* row16_scale, float w3_norm, float b3_max,
+                           ev2h_stream_t stream);
+int ev2h_dbg_gemm_zsum_supported(const ev2h_gemm_desc* d);
+int ev2h_dbg_gemm_zsum(const ev2h_gemm_desc* d, const float* key_pm, float* zpart, int x_16, const float* x_scale, ev2h_stream_t stream);
+int ev2h_dbg_attn_simfold_partials(const float* zpart, int rows_per_partial, const float* logits_pm, int B, int N, const float* w4t_left,
+                                   const float* w4t_right, const float* b4_left, const float* b4_right, float* sim, ev2h_stream_t stream);
+int ev2h_dbg_attn_context_rows16(const float* sim, const void* value16, int ldv, int B, int N, float* hf8, uint32_t* hf_amax,
+                                 int amax_hand_stride, const float* value_unscale, const float* vscale, ev2h_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

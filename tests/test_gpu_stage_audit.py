@@ -2,9 +2,11 @@
 
 tests/test_gpu_ops.py holds each operator to its bar on hash-normal inputs through its C entry point; tests/test_gpu_forward.py
 holds the whole forward's outputs to 1e-4 (fp32-class modes), 2e-2 (bf16) or a few 1e-3 (f16).  Between the two an fp32 stage
-that is 1e-3 off in a 16-bit mode passes, and the kernels without a C entry point (the 16-bit-row attention contexts, the fold
-over the GEMM's own 128-row partials, the three-job sampling, the [features | xyz] hand-off columns, fp3's per-window bias) are
-only ever seen through the final outputs.
+that is 1e-3 off in a 16-bit mode passes, and what no operator entry point reaches (the three-job sampling, the [features | xyz]
+hand-off columns, fp3's per-window bias) is only ever seen through the final outputs.  (The kernels of the fused tail -- the
+16-bit-row chains and attention contexts, the query convolution with the partial sums as its epilogue, the fold over those 128-row
+partials -- have test hooks, and tests/test_gpu_fused_tail.py holds each of them to float64 on inputs of its own; here they are seen
+on the forward's own data.)
 
 Here each stage's INPUTS are taken from the workspace as the GPU wrote them (TEHNet.debug_buffer, un-equalised), the stage alone
 is evaluated in float64 on the device (tests/ref_stages.py, proved equal to the oracle by tests/test_stage_refs_cpu.py), and the
