@@ -99,7 +99,8 @@ W_EQUALIZED, W_UNEQUALIZED_OK = 1, 2
 # ev2h_joint_metrics_f32_frames, ev2h_segmentation_score, ev2h_eval_s_accumulate), and for the loss exports (ev2h_loss_terms,
 # ev2h_loss_accumulate), and for the augmented training item (ev2h_event_window_build_s_ranges_aug), and for the fine-tuning item
 # (ev2h_event_window_build_ranges_flip, ev2h_finetune_resolve, ev2h_finetune_targets), and for the gradient exports (ev2h_mano_backward,
-# ev2h_segmentation_score_backward, ev2h_loss_terms_backward, ev2h_collision_penalty_backward), and for the test hooks (ev2h_dbg_*).
+# ev2h_segmentation_score_backward, ev2h_loss_terms_backward, ev2h_collision_penalty_backward), and for the test hooks (ev2h_dbg_*),
+# and for the fitting exports (ev2h_mano_joints_jacobian, ev2h_mano_fit, ev2h_mano_fit_opts_size).
 ABI_VERSION = 8     # 8: EV2H_PREC_F16 (one fp16 plane with f16x2's range machinery); 3: F16X2 range records; 4: ev2h_fp_mlp, ev2h_weights.fp1m; 5: window strides of the outputs; 6: ev2h_pack_weights, ev2h_weights.flags; 7: ev2h_sa_desc.xyz_out
 
 PREC = {"f32": 0, "bf16": 1, "f16x2": 2, "bf16x3": 3, "f16": 4}
@@ -109,6 +110,14 @@ class ManoConsts(C.Structure):
     _fields_ = [("hands_mean", vp), ("comps", vp), ("blend_T", vp), ("v_template", vp),
                 ("J_template", vp), ("J_shape", vp), ("weights", vp),
                 ("tips", C.c_int32 * 5), ("ncomps", C.c_int32)]
+
+
+class ManoFitOpts(C.Structure):
+    _fields_ = [("lam_pose", C.c_double), ("lam_shape", C.c_double), ("mu0", C.c_double), ("ftol", C.c_double),
+                ("max_iters", C.c_int32), ("free_mask", C.c_int32)]
+
+
+FIT_GROUPS = ("global_orient", "hand_pose", "betas", "transl")      # bits 0..3 of ev2h_mano_fit_opts.free_mask
 
 
 class Outputs(C.Structure):
@@ -135,6 +144,7 @@ EXPORTS = [
     "ev2h_event_window_build_s_ranges_aug",
     "ev2h_event_window_build_ranges_flip", "ev2h_finetune_resolve", "ev2h_finetune_targets",
     "ev2h_mano_backward", "ev2h_segmentation_score_backward", "ev2h_loss_terms_backward", "ev2h_collision_penalty_backward",
+    "ev2h_mano_joints_jacobian", "ev2h_mano_fit", "ev2h_mano_fit_opts_size",
     # test hooks, not part of the stable interface (include/ev2hands_hip.h: "Test hooks"; ev2hands_amd/ops.py: *_rows16, dense_zsum, ...)
     "ev2h_dbg_fp_mlp_rows16", "ev2h_dbg_gemm_zsum_supported", "ev2h_dbg_gemm_zsum", "ev2h_dbg_attn_simfold_partials", "ev2h_dbg_attn_context_rows16",
 ]
@@ -239,6 +249,10 @@ def lib() -> C.CDLL:
     L.ev2h_collision_penalty_backward.argtypes = [vp, vp, vp, vp, ci, ci, ci, C.c_float, C.c_double, vp, vp, ci, vp, vp, vp]
     L.ev2h_mano_backward.argtypes = [C.POINTER(ManoConsts), vp, ci, ci, vp, C.c_size_t, vp, C.c_size_t, vp, C.c_size_t, ci, vp]
     L.ev2h_segmentation_score_backward.argtypes = [vp, C.c_size_t, vp, ci, ci, vp, vp, C.c_size_t, vp]
+    L.ev2h_mano_joints_jacobian.argtypes = [C.POINTER(ManoConsts), vp, ci, ci, vp, vp, vp]
+    L.ev2h_mano_fit.argtypes = [C.POINTER(ManoConsts), vp, ci, ci, vp, C.c_size_t, vp, C.c_size_t, C.POINTER(ManoFitOpts), vp, C.c_size_t, vp, vp, vp]
+    L.ev2h_mano_fit_opts_size.restype = C.c_size_t
+    L.ev2h_mano_fit_opts_size.argtypes = []
     L.ev2h_dbg_fp_mlp_rows16.argtypes = [C.POINTER(FpDesc), ci, ci, vp, C.c_float, C.c_float, vp]
     L.ev2h_dbg_gemm_zsum_supported.argtypes = [C.POINTER(GemmDesc)]
     L.ev2h_dbg_gemm_zsum.argtypes = [C.POINTER(GemmDesc), vp, vp, ci, vp, vp]
@@ -278,6 +292,8 @@ def lib() -> C.CDLL:
     mine = [C.sizeof(t) for t in (GemmDesc, SaDesc, SaModule, Weights, ManoConsts, Outputs, FpDesc, TensorDesc)]
     if list(sizes) != mine:
         raise Ev2hError(f"struct layout mismatch between ev2hands_hip.h and _lib.py: {list(sizes)} vs {mine}")
+    if L.ev2h_mano_fit_opts_size() != C.sizeof(ManoFitOpts):
+        raise Ev2hError(f"struct layout mismatch between ev2hands_hip.h and _lib.py: ev2h_mano_fit_opts {L.ev2h_mano_fit_opts_size()} vs {C.sizeof(ManoFitOpts)}")
     if L.ev2h_abi_version() != ABI_VERSION:
         raise Ev2hError(f"ABI version mismatch: library {L.ev2h_abi_version()}, binding {ABI_VERSION}")
     _lib = L

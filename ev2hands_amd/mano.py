@@ -156,6 +156,144 @@ class ManoHand:
                                                  _lib.stream_handle()), "ev2h_mano_backward")
         return out
 
+    def _rows(self, t, name):
+        """the check `vjp` makes of its parameter rows: float32 [B, P] on the device, rows dense and not overlapping -> (B, row stride)"""
+        P = 16 + self.ncomps
+        if not isinstance(t, torch.Tensor) or t.dim() != 2 or t.shape[0] < 1:
+            raise ValueError(f"{name} must be a float32 [B, {P}] CUDA tensor with B >= 1")
+        B = int(t.shape[0])
+        _lib._dev_tensor(t, name, torch.float32, (B, P), self.device, contiguous=False)
+        if t.stride(1) != 1 or (B > 1 and t.stride(0) < P):
+            raise ValueError(f"{name}: rows must be dense and must not overlap, got strides {t.stride()}")
+        return B, (int(t.stride(0)) if B > 1 else P)
+
+    def joints_jacobian(self, params):
+        """ev2h_mano_joints_jacobian: params float32 [B, 16 + ncomps] (as `vjp` takes them) -> (joints float64 [B, 21, 3] in metres,
+        jac float64 [B, 63, 16 + ncomps]: row 3 * j + c = d joints[j][c] / d params).  No host synchronisation."""
+        B, ldp = self._rows(params, "params")
+        P = 16 + self.ncomps
+        joints = torch.empty(B, 21, 3, device=self.device, dtype=torch.float64)
+        jac = torch.empty(B, 63, P, device=self.device, dtype=torch.float64)
+        c = self.consts()
+        _lib.check(_lib.lib().ev2h_mano_joints_jacobian(C.byref(c), params.data_ptr(), ldp, B, joints.data_ptr(), jac.data_ptr(), _lib.stream_handle()),
+                   "ev2h_mano_joints_jacobian")
+        return joints, jac
+
+    def rest_joints(self):
+        """the joints of the zero parameter row, float64 [21, 3] on the device; evaluated once per packing of the constants"""
+        c = self.consts()
+        if getattr(self, "_rest_of", None) is not c:
+            zero = torch.zeros(1, 16 + self.ncomps, device=self.device, dtype=torch.float32)
+            self._rest, self._rest_of = self.joints_jacobian(zero)[0][0], c
+        return self._rest
+
+    def fit(self, j3d, weights=None, init=None, lam_pose: float = 0.0, lam_shape: float = 0.0, free=_lib.FIT_GROUPS, max_iters: int = 32,
+            mu0: float = 1e-3, ftol: float = 1e-12):
+        """ev2h_mano_fit: fit the parameter rows to the 3-D joints j3d (float32 [B, 21, 3] in metres, dense windows that do not
+        overlap) by Levenberg-Marquardt, every window's whole loop inside one launch (include/ev2hands_hip.h states the algorithm).
+        weights: [B, 21] >= 0 (a joint of weight 0 is left out; its target may be NaN), None = ones.  init: float32 [B, 16 + ncomps]
+        start rows (such as the network's), None = zeros, or "rigid" = global_orient and transl from the rigid alignment of the rest
+        pose's joints onto the targets (`rigid_init`), the other groups zero.  lam_pose / lam_shape: prior weights on hand_pose /
+        betas.  free: the groups that move; the others stay at `init`.  -> ManoFit.  No host synchronisation."""
+        P = 16 + self.ncomps
+        if not isinstance(j3d, torch.Tensor) or j3d.dim() != 3 or j3d.shape[0] < 1:
+            raise ValueError("j3d must be a float32 [B, 21, 3] CUDA tensor with B >= 1")
+        B = int(j3d.shape[0])
+        _lib._dev_tensor(j3d, "j3d", torch.float32, (B, 21, 3), self.device, contiguous=False)
+        if j3d.stride()[1:] != (3, 1) or (B > 1 and j3d.stride(0) < 63):
+            raise ValueError(f"j3d: windows must be dense and must not overlap, got strides {j3d.stride()}")
+        if weights is not None:
+            if not isinstance(weights, torch.Tensor) or tuple(weights.shape) != (B, 21) or weights.device != self.device or \
+                    not (weights.dtype.is_floating_point or weights.dtype == torch.bool):
+                raise ValueError(f"weights must be a floating-point or bool tensor [{B}, 21] on {self.device}")
+            if weights.dtype != torch.float32 or weights.stride(1) != 1 or (B > 1 and weights.stride(0) < 21):
+                weights = weights.to(torch.float32).contiguous()
+        unknown = [g for g in free if g not in _lib.FIT_GROUPS]
+        if unknown or isinstance(free, str):
+            raise ValueError(f"free holds names of {_lib.FIT_GROUPS}, got {free!r}")
+        if isinstance(init, str):
+            if init != "rigid":
+                raise ValueError('init is a float32 tensor, None or "rigid"')
+            go, tr = rigid_init(self.rest_joints(), j3d, weights)
+            init = torch.zeros(B, P, device=self.device, dtype=torch.float32)
+            init[:, :3], init[:, 13 + self.ncomps:] = go, tr
+        elif init is None:
+            init = torch.zeros(B, P, device=self.device, dtype=torch.float32)
+        if self._rows(init, "init")[0] != B:
+            raise ValueError(f"init must have {B} rows")
+        opts = _lib.ManoFitOpts(float(lam_pose), float(lam_shape), float(mu0), float(ftol), int(max_iters),
+                                sum(1 << i for i, g in enumerate(_lib.FIT_GROUPS) if g in free))
+        out = torch.empty(B, P, device=self.device, dtype=torch.float64)
+        stats = torch.empty(B, 4, device=self.device, dtype=torch.float64)
+        info = torch.empty(B, 2, device=self.device, dtype=torch.int32)
+        c = self.consts()
+        _lib.check(_lib.lib().ev2h_mano_fit(C.byref(c), init.data_ptr(), int(init.stride(0)) if B > 1 else P, B, j3d.data_ptr(),
+                                            int(j3d.stride(0)) if B > 1 else 0, _lib.ptr(weights), int(weights.stride(0)) if weights is not None and B > 1 else 0,
+                                            C.byref(opts), out.data_ptr(), 0, stats.data_ptr(), info.data_ptr(), _lib.stream_handle()), "ev2h_mano_fit")
+        return ManoFit(self, out, stats, info)
+
+
+class ManoFit:
+    """What ManoHand.fit returns, all device tensors: `params64` float64 [B, 16 + ncomps] (the last accepted rows), `params` = the same
+    rounded once to float32 and its views `global_orient`, `hand_pose`, `betas`, `transl`; `cost0` / `cost` float64 [B] (the squared
+    residual norm in mm^2, priors included, at the start and at the end), `mu`, `gmax` (the final damping, max |J^T r| of the last
+    linearisation), `iterations` and `status` int32 [B] (0 converged, 1 max_iters reached, 2 non-finite input: the row is the
+    start row).  `output`: the layer's float32 forward of the rounded rows, evaluated when first asked for."""
+
+    def __init__(self, hand, params64, stats, info):
+        K = hand.ncomps
+        self._hand, self._output = hand, None
+        self.params64, self.params = params64, params64.to(torch.float32)
+        self.global_orient, self.hand_pose = self.params[:, :3], self.params[:, 3:3 + K]
+        self.betas, self.transl = self.params[:, 3 + K:13 + K], self.params[:, 13 + K:]
+        self.cost0, self.cost, self.mu, self.gmax = stats[:, 0], stats[:, 1], stats[:, 2], stats[:, 3]
+        self.iterations, self.status = info[:, 0], info[:, 1]
+
+    @property
+    def output(self):
+        if self._output is None:
+            with torch.no_grad():
+                self._output = self._hand(global_orient=self.global_orient, hand_pose=self.hand_pose, betas=self.betas, transl=self.transl)
+        return self._output
+
+
+def axis_angle(R):
+    """rotation matrices [B, 3, 3] -> axis-angle vectors [B, 3] (angle in [0, pi]), torch operations on R's device"""
+    v = torch.stack([R[:, 2, 1] - R[:, 1, 2], R[:, 0, 2] - R[:, 2, 0], R[:, 1, 0] - R[:, 0, 1]], 1)          # 2 sin(angle) axis
+    s = v.norm(dim=1)
+    c = R.diagonal(dim1=1, dim2=2).sum(1) - 1.0                                                          # 2 cos(angle)
+    ang = torch.atan2(s, c)
+    general = v / s.clamp_min(1e-300)[:, None]
+    # near pi the antisymmetric part vanishes: R + I = 2 n n^T there; its column with the largest diagonal, signed like v
+    M = R + torch.eye(3, dtype=R.dtype, device=R.device)
+    col = torch.gather(M, 2, M.diagonal(dim1=1, dim2=2).argmax(1)[:, None, None].expand(-1, 3, 1))[:, :, 0]
+    col = col / col.norm(dim=1).clamp_min(1e-300)[:, None]
+    sign = torch.where((col * v).sum(1) < 0, -torch.ones_like(s), torch.ones_like(s))
+    near_pi = (s < 1e-6) & (c < 0)
+    return torch.where(near_pi[:, None], col * sign[:, None], general) * ang[:, None]
+
+
+def rigid_init(rest, j3d, weights=None):
+    """The start of ManoHand.fit(init="rigid"): the least-squares rigid alignment (Kabsch) of the rest pose's joints `rest` [21, 3]
+    onto the targets j3d [B, 21, 3], over the joints of positive weight ([B, 21]; None = all).  -> (global_orient, transl) float64
+    [B, 3] each: the layer turns the hand about its root joint, so transl = t + R rest_root - rest_root for j3d ~ R rest + t.
+    torch operations on j3d's device (torch.linalg.svd with the determinant fix); set-up work, not the hot path."""
+    rest = rest.to(j3d.device, torch.float64)
+    B = j3d.shape[0]
+    on = torch.ones(B, 21, dtype=torch.bool, device=j3d.device) if weights is None else weights.to(j3d.device) > 0
+    m = on.to(torch.float64)[..., None]
+    tgt = torch.where(on[..., None], j3d.to(torch.float64), torch.zeros((), dtype=torch.float64, device=j3d.device))
+    n = m.sum(1).clamp_min(1.0)
+    cs, cd = (m * rest[None]).sum(1) / n, (m * tgt).sum(1) / n
+    X, Y = (rest[None] - cs[:, None]) * m, (tgt - cd[:, None]) * m
+    U, _, Vh = torch.linalg.svd(torch.einsum("bni,bnj->bij", Y, X))
+    d = torch.where(torch.linalg.det(U @ Vh) < 0, -1.0, 1.0).to(torch.float64)
+    D = torch.diag_embed(torch.stack([torch.ones_like(d), torch.ones_like(d), d], 1))
+    R = U @ D @ Vh
+    t = cd - torch.einsum("bij,bj->bi", R, cs)
+    root = rest[0]
+    return axis_angle(R), t + torch.einsum("bij,j->bi", R, root) - root[None]
+
 
 class _ManoFunction(torch.autograd.Function):
     """ManoHand.__call__ for inputs that require grad: ev2h_mano forward, ManoHand.vjp backward."""

@@ -196,6 +196,24 @@ class RecordingSet:
     def __len__(self) -> int:
         return self.n_rows
 
+    def fit_mano(self, hands, recording: int, **fit_kwargs) -> dict:
+        """MANO rows for a recording's joints: ManoHand.fit of `hands` ({'left', 'right'}, mano.create_mano_layers) on the recording's
+        [F, 2, 21, 3] joints in metres, one row per frame.  A frame's hand whose joints are not all finite gets weight 0 throughout
+        (its row stays the start row while no prior is set).  fit_kwargs: ManoHand.fit's (init, lam_pose, free, ...; `weights`
+        [F, 21] is multiplied in).  -> {'left': ManoFit, 'right': ManoFit}.  No host synchronisation."""
+        if not 0 <= int(recording) < self.n_recordings:
+            raise ValueError(f"recording must be 0 .. {self.n_recordings - 1}")
+        joints = self.joints[self.joint_rows[int(recording)]:self.joint_rows[int(recording) + 1]]
+        extra = fit_kwargs.pop("weights", None)
+        out = {}
+        for h, side in enumerate(("left", "right")):
+            j = joints[:, h]
+            w = torch.isfinite(j).all(2).all(1).to(torch.float32)[:, None].expand(-1, 21)
+            if extra is not None:
+                w = w * extra.to(self.device, torch.float32)
+            out[side] = hands[side].fit(j.to(torch.float32).contiguous(), weights=w.contiguous(), **fit_kwargs)
+        return out
+
 
 class TrainingBatcherR:
     """The collated fine-tuning batch for items of a RecordingSet.  reference_quirks=True is the reference's item: augment_events

@@ -392,6 +392,44 @@ int ev2h_mano_rotations(const ev2h_mano_consts* c, const float* params, int ldp,
 int ev2h_mano_backward(const ev2h_mano_consts* c, const float* params, int ldp, int B, const double* g_verts, size_t g_verts_stride,
                        const double* g_joints, size_t g_joints_stride, double* g_params, size_t g_params_stride, int accumulate,
                        ev2h_stream_t stream);
+/* The Jacobian of ev2h_mano's 21 joints (csrc/mano_fit.hip), P = 16 + ncomps: jac [B][63][P] float64, row 3 * j + c =
+ * d joints[j][c] / d params in metres per parameter unit, the joints in the layer's output order with transl added;
+ * joints [B][21][3] float64 (may be NULL) = the joints themselves.  Arithmetic: ev2h_mano_backward's rule (float32 parameters and
+ * constants widened, float64 throughout, theta + 1e-8 inside the norm).  Forward mode: one workgroup per window, lane p carries the
+ * tangent of parameter p through the 16 rotations, the chain and the five fingertip vertices (the other 773 are not computed).
+ * Fixed summation order, no atomics: the same call gives the same bytes, window b's depend on window b's row alone.
+ * EV2H_ERR_ARG before any device call: a null c / params / jac / constant, B < 1, ncomps outside 1..45, ldp < P, a fingertip
+ * vertex outside 0..777.  One launch, no host synchronisation, capturable. */
+int ev2h_mano_joints_jacobian(const ev2h_mano_consts* c, const float* params, int ldp, int B, double* joints, double* jac,
+                              ev2h_stream_t stream);
+typedef struct ev2h_mano_fit_opts {
+    double lam_pose;             /* >= 0: prior weight on hand_pose                                                   */
+    double lam_shape;            /* >= 0: prior weight on betas                                                       */
+    double mu0;                  /* >= 0: initial damping                                                             */
+    double ftol;                 /* >= 0: stop after an accepted step with cost - cost' <= ftol * cost                */
+    int32_t max_iters;           /* 1..64 solves per window                                                           */
+    int32_t free_mask;           /* bit 0 global_orient, 1 hand_pose, 2 betas, 3 transl; a cleared bit freezes the group at params0 */
+} ev2h_mano_fit_opts;
+size_t ev2h_mano_fit_opts_size(void);      /* sizeof(ev2h_mano_fit_opts), for the binding's layout check (ev2h_struct_sizes keeps its eight) */
+/* Fit the parameter rows to 3-D joints (csrc/mano_fit.hip): Levenberg-Marquardt, the whole loop of a window inside one workgroup of
+ * one launch, float64, no host read.  params0 [B][ldp] float32 start rows; targets [B][21][3] metres (window b at + b *
+ * targets_stride floats, 0 = 63); weights [B][21] >= 0 (stride 0 = 21; NULL = all 1).
+ *   residuals (mm): for w_j > 0 the rows sqrt(w_j) * 1000 * (joint_j - t_j); a joint with w_j == 0 is left out by selection (its
+ *     target may be NaN); then ncomps rows sqrt(lam_pose) * hand_pose_k and 10 rows sqrt(lam_shape) * betas_k.  cost = |r|^2.
+ *   H = J^T J, g = J^T r (rows in index order); a frozen parameter has a zero row and column, diagonal 1 and g 0.
+ *   step: D_ii = H_ii where H_ii > 0 else 1; Cholesky of H + mu D; (H + mu D) delta = -g; a pivot that is not finite or not
+ *     positive is a rejected step.  cost' finite and < cost: accept, mu <- max(mu / 10, 1e-12); else mu <- min(10 mu, 1e12).
+ *     Every solve is an iteration.  Stop after an accepted step with cost - cost' <= ftol * cost, when cost == 0, at max_iters.
+ * params_out [B][P] float64 (stride 0 = P): the last accepted row.  stats [B][4] = {cost at params0, final cost, final mu, max|g| of
+ * the last linearisation}.  info [B][2] = {iterations, status}: 0 converged, 1 max_iters reached, 2 a non-finite params0 or a
+ * non-finite target of positive weight (params_out = params0 widened, 0 iterations, stats = {NaN, NaN, mu0, NaN}).
+ * Window b's outputs depend on window b's inputs and opts only; the same call gives the same bytes.
+ * EV2H_ERR_ARG before any device call: a null c / params0 / targets / opts / params_out / stats / info / constant, B < 1, ldp < P,
+ * a stride below its dense window, max_iters outside 1..64, a negative or non-finite prior, mu0 or ftol, ncomps outside 1..45, a
+ * fingertip vertex outside 0..777. */
+int ev2h_mano_fit(const ev2h_mano_consts* c, const float* params0, int ldp, int B, const float* targets, size_t targets_stride,
+                  const float* weights, size_t weights_stride, const ev2h_mano_fit_opts* opts, double* params_out, size_t out_stride,
+                  double* stats, int32_t* info, ev2h_stream_t stream);
 
 /* ---- event window -> [5, N] tensor (next row 8f-1; dataset/evaluation_stream.py:187-225, ev2hands_r.py:108-159, erpc.py:169-249) ---- */
 /* Per-pixel accumulation + np.nonzero-order compaction of B ragged windows.  events: device float64 rows of ev_stride (>= 4)
