@@ -100,7 +100,8 @@ W_EQUALIZED, W_UNEQUALIZED_OK = 1, 2
 # ev2h_loss_accumulate), and for the augmented training item (ev2h_event_window_build_s_ranges_aug), and for the fine-tuning item
 # (ev2h_event_window_build_ranges_flip, ev2h_finetune_resolve, ev2h_finetune_targets), and for the gradient exports (ev2h_mano_backward,
 # ev2h_segmentation_score_backward, ev2h_loss_terms_backward, ev2h_collision_penalty_backward), and for the test hooks (ev2h_dbg_*),
-# and for the fitting exports (ev2h_mano_joints_jacobian, ev2h_mano_fit, ev2h_mano_fit_opts_size).
+# and for the fitting exports (ev2h_mano_joints_jacobian, ev2h_mano_fit, ev2h_mano_fit_opts_size), and for the event simulator
+# (ev2h_esim_scratch_bytes, ev2h_esim_step, ev2h_esim_compose).
 ABI_VERSION = 8     # 8: EV2H_PREC_F16 (one fp16 plane with f16x2's range machinery); 3: F16X2 range records; 4: ev2h_fp_mlp, ev2h_weights.fp1m; 5: window strides of the outputs; 6: ev2h_pack_weights, ev2h_weights.flags; 7: ev2h_sa_desc.xyz_out
 
 PREC = {"f32": 0, "bf16": 1, "f16x2": 2, "bf16x3": 3, "f16": 4}
@@ -117,6 +118,8 @@ class ManoFitOpts(C.Structure):
                 ("max_iters", C.c_int32), ("free_mask", C.c_int32)]
 
 
+ESIM_MODES = {"frame": 0, "scaled": 1, "interpolated": 2}      # EV2H_ESIM_FRAME, _FRAME_SCALED, _INTERPOLATED
+ESIM_OVER_CAPACITY, ESIM_LOOP_BOUND, ESIM_OVER_SORT = 1, 2, 4     # the status bits of ev2h_esim_step's state[3]
 FIT_GROUPS = ("global_orient", "hand_pose", "betas", "transl")      # bits 0..3 of ev2h_mano_fit_opts.free_mask
 
 
@@ -145,6 +148,7 @@ EXPORTS = [
     "ev2h_event_window_build_ranges_flip", "ev2h_finetune_resolve", "ev2h_finetune_targets",
     "ev2h_mano_backward", "ev2h_segmentation_score_backward", "ev2h_loss_terms_backward", "ev2h_collision_penalty_backward",
     "ev2h_mano_joints_jacobian", "ev2h_mano_fit", "ev2h_mano_fit_opts_size",
+    "ev2h_esim_scratch_bytes", "ev2h_esim_step", "ev2h_esim_compose",
     # test hooks, not part of the stable interface (include/ev2hands_hip.h: "Test hooks"; ev2hands_amd/ops.py: *_rows16, dense_zsum, ...)
     "ev2h_dbg_fp_mlp_rows16", "ev2h_dbg_gemm_zsum_supported", "ev2h_dbg_gemm_zsum", "ev2h_dbg_attn_simfold_partials", "ev2h_dbg_attn_context_rows16",
 ]
@@ -253,6 +257,11 @@ def lib() -> C.CDLL:
     L.ev2h_mano_fit.argtypes = [C.POINTER(ManoConsts), vp, ci, ci, vp, C.c_size_t, vp, C.c_size_t, C.POINTER(ManoFitOpts), vp, C.c_size_t, vp, vp, vp]
     L.ev2h_mano_fit_opts_size.restype = C.c_size_t
     L.ev2h_mano_fit_opts_size.argtypes = []
+    L.ev2h_esim_scratch_bytes.restype = C.c_size_t
+    L.ev2h_esim_scratch_bytes.argtypes = [ci, ci, ci, ci, ci]
+    L.ev2h_esim_step.argtypes = [vp, ci, ci, ci, vp, ci, vp, vp, C.c_double, C.c_double, C.c_double, C.c_double, ci, ci, ci, vp, vp, vp, vp,
+                                 ci, vp, ci, vp, C.c_size_t, vp]
+    L.ev2h_esim_compose.argtypes = [vp, vp, vp, ci, ci, ci, ci, ci, ci, vp, vp]
     L.ev2h_dbg_fp_mlp_rows16.argtypes = [C.POINTER(FpDesc), ci, ci, vp, C.c_float, C.c_float, vp]
     L.ev2h_dbg_gemm_zsum_supported.argtypes = [C.POINTER(GemmDesc)]
     L.ev2h_dbg_gemm_zsum.argtypes = [C.POINTER(GemmDesc), vp, vp, ci, vp, vp]

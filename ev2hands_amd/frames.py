@@ -206,12 +206,25 @@ class DemoFrames:
         self._points_into(pix, class_logits, ls, frame, 1, -1, 0)
         return frame
 
-    def render(self, verts_left, verts_right, return_buffers: bool = False):
+    def render(self, verts_left, verts_right, return_buffers: bool = False, out=None):
         """uint8 [B,H,W,3]: panel 3 for verts_* [B,nv,3] float32 metres (the forward's out[side]['vertices']).  return_buffers: also
-        depth float32 [B,H,W] (mm, 0 = background) and face_id int32 [B,H,W] (-1 = background, 0..nf-1 left hand, nf..2nf-1 right)."""
+        depth float32 [B,H,W] (mm, 0 = background) and face_id int32 [B,H,W] (-1 = background, 0..nf-1 left hand, nf..2nf-1 right).
+        out: caller-owned (frame, depth or None, face_id or None) to write into; with it (and scratch sized by `max_batch`) the call
+        allocates nothing, and it returns that triple."""
         B = verts_left.shape[0] if torch.is_tensor(verts_left) and verts_left.dim() == 3 else None
         self._check_verts(verts_left, "verts_left")
         self._check_verts(verts_right, "verts_right", B)
+        if out is not None:
+            frame, depth, face_id = out
+            self._check_frame(frame, "out[0]", B, 1)
+            if depth is not None:
+                self._check(depth, "out[1]", torch.float32, (B, self.h, self.w))
+            if face_id is not None:
+                self._check(face_id, "out[2]", torch.int32, (B, self.h, self.w))
+            if (depth is not None and not depth.is_contiguous()) or (face_id is not None and not face_id.is_contiguous()):
+                raise ValueError("DemoFrames: depth and face_id must be contiguous")
+            self._render_into(verts_left, verts_right, frame, 1, 0, 0, depth, face_id)
+            return frame, depth, face_id
         frame = torch.empty(B, self.h, self.w, 3, device=self.device, dtype=torch.uint8)
         depth = torch.empty(B, self.h, self.w, device=self.device, dtype=torch.float32) if return_buffers else None
         face_id = torch.empty(B, self.h, self.w, device=self.device, dtype=torch.int32) if return_buffers else None

@@ -1,0 +1,238 @@
+"""Ev2Hands-S event tables on the GPU, from MANO pose sequences: the reference's HandSimulator (/root/reference/src/HandSimulator:
+main.py, renderer.py, color_event_simulator.py, stich_mp.py) without its files.
+
+    sim = EventSimulatorS(device, net.hands, fps=1000, timestamps="interpolated")
+    sim.begin()                                          # every buffer is allocated here; resets the state
+    sim.step(params_left, params_right)                  # float32 [F, 16 + K] each: MANO -> render -> compose -> events
+    table, info = sim.finish()                           # the ONE host read: an EventTableS over the written rows
+    batcher = TrainingBatcherS(device, None, annotation_table=(sim.annotation_table(params_left, params_right), flags))
+
+What is PINNED: `step_images` with timestamps="frame" is the reference's ColorEventSimulator (its CPU driver) bit for bit -- events,
+their order, the memory frame, the annotation indices of main.py:71-75 / stich_mp.py:40 and the labels of main.py:87
+(tests/golden/events_esim_frames_*.npz hold the reference's own outputs).  "scaled" is the same with t = frame * 1e9 / fps, the nanoseconds
+Ev2HandSDataset expects.
+
+What is the PROJECT'S OWN: timestamps="interpolated" is ESIM's rule (linear crossing times between two frames) applied to this
+simulator's memory frame, stated in include/ev2hands_hip.h and tests/ref_esim.py; the reference's ColorESIM calls esim_torch, a CUDA
+extension that is not part of the reference tree, so parity with it is UNPINNED.  The frames `step` feeds the generator are DemoFrames'
+render (csrc/render.hip, itself unpinned against pyrender) coloured with one `hand_color` over a fixed `background`: not pyrender with
+UV textures, random lights and background images.  The labels are the render's own face_id (0 background, 1 left, 2 right), which is
+what the reference's segmentation render encodes.
+
+NOT provided: UV textures, lights, background image sets, the InterHand readers, pose interpolation (augmentations.interpolate_sequence),
+camera transforms of the parameter rows (the rows are camera-space, as camera_hand_info is) and .h5 / pickle writing.
+
+Every buffer is allocated in `begin`: `step_images` and `step` synchronise nothing, allocate nothing and read nothing back; `finish`
+reads the counters once.
+"""
+from __future__ import annotations
+
+import ctypes as C
+
+import numpy as np
+import torch
+
+from . import _lib
+from ._lib import _dev_tensor
+from .events import OUTPUT_HEIGHT, OUTPUT_WIDTH, EventTableS
+from .frames import DemoFrames
+
+BACKGROUND_GREY = 159                      # color_event_simulator.py:151: the grey the reference's memory frame starts from
+_STATE_WORDS = 16                          # int64[8] as int32 words, in front of annotation_frame in one buffer (one host read)
+
+
+def log_table() -> np.ndarray:
+    """float64 [256]: the log value of a byte, color_event_simulator.py:176-180 applied to the 256 byte values"""
+    return np.log(((np.arange(256).astype(np.uint8).astype(np.float32) / 255) ** 2.2).astype(np.float64) + 1e-4)
+
+
+def initial_mem_value() -> float:
+    bg_val = BACKGROUND_GREY / 255.
+    return float(np.log(bg_val ** 2.2 + 0.01))           # color_event_simulator.py:150-152
+
+
+class EventSimulatorS:
+    """hands: {'left', 'right'} of ManoHand (net.hands).  threshold_pos / threshold_neg / eps: the contrast thresholds (the reference:
+    0.4, 0.4, 1e-6; both thresholds must exceed 2 eps).  timestamps: "frame" | "scaled" | "interpolated" (module docstring).
+    capacity: rows of the table; max_annotations: entries of annotation_frame; chunk: the most frames one step takes;
+    max_per_pixel (<= 127): the bound of a pixel's events in one frame; max_events_per_frame (<= 8192): the interpolated order's
+    sort capacity.  background: uint8 [H, W, 3] (default all 159); hand_color: RGB.  f, cx, cy: the camera (DemoFrames' defaults)."""
+
+    def __init__(self, device, hands, fps: float = 1000, threshold_pos: float = 0.4, threshold_neg: float = 0.4, eps: float = 1e-6,
+                 timestamps: str = "interpolated", width: int = OUTPUT_WIDTH, height: int = OUTPUT_HEIGHT, capacity: int = 4_000_000,
+                 chunk: int = 64, background=None, hand_color=(198, 134, 66), max_per_pixel: int = 64, max_events_per_frame: int = 8192,
+                 max_annotations: int = 65536, f: float | None = None, cx: float | None = None, cy: float | None = None):
+        self.device = torch.zeros(0, device=device).device
+        if self.device.type != "cuda":
+            raise RuntimeError("EventSimulatorS runs on the GPU only (there is no CPU fallback)")
+        if timestamps not in _lib.ESIM_MODES:
+            raise ValueError(f"timestamps must be one of {tuple(_lib.ESIM_MODES)}, got {timestamps!r}")
+        self.mode, self.timestamps = _lib.ESIM_MODES[timestamps], timestamps
+        self.fps, self.tp, self.tn, self.eps = float(fps), float(threshold_pos), float(threshold_neg), float(eps)
+        self.w, self.h, self.capacity, self.chunk = int(width), int(height), int(capacity), int(chunk)
+        self.max_pp, self.mepf, self.max_annotations = int(max_per_pixel), int(max_events_per_frame), int(max_annotations)
+        if not (self.tp > 2 * self.eps and self.tn > 2 * self.eps and self.eps >= 0):
+            raise ValueError("threshold_pos > 2 eps, threshold_neg > 2 eps and eps >= 0 required (else both loops could run for one pixel)")
+        if not (self.fps > 0 and 1 <= self.capacity < 2 ** 31 and 1 <= self.chunk <= 4096 and 1 <= self.max_pp <= 127 and 1 <= self.mepf <= 8192
+                and self.max_annotations >= 1 and self.w >= 1 and self.h >= 1):
+            raise ValueError("fps > 0, 1 <= capacity < 2**31, 1 <= chunk <= 4096, 1 <= max_per_pixel <= 127, 1 <= max_events_per_frame <= 8192 required")
+        self.hand_color = tuple(int(c) for c in hand_color)
+        if len(self.hand_color) != 3 or not all(0 <= c <= 255 for c in self.hand_color):
+            raise ValueError("hand_color must be three bytes (R, G, B)")
+        bg = np.full((self.h, self.w, 3), BACKGROUND_GREY, dtype=np.uint8) if background is None else np.asarray(
+            background.cpu() if torch.is_tensor(background) else background)
+        if bg.dtype != np.uint8 or bg.shape != (self.h, self.w, 3):
+            raise ValueError(f"background must be uint8 [{self.h}, {self.w}, 3]")
+        self.background = torch.from_numpy(np.ascontiguousarray(bg)).to(self.device)
+        self.hands = hands
+        self.frames, self.nf = None, 0
+        if hands is not None:
+            self.frames = DemoFrames(self.device, hands["left"].faces, hands["right"].faces, self.w, self.h, f=f, cx=cx, cy=cy, max_batch=self.chunk)
+            self.nf = self.frames.nf
+        self.table = torch.from_numpy(log_table()).to(self.device)
+        self.scratch_bytes = int(_lib.lib().ev2h_esim_scratch_bytes(self.chunk, self.w, self.h, self.mode, self.mepf))
+        if self.scratch_bytes == 0:
+            raise ValueError("chunk, width, height or max_events_per_frame out of range (include/ev2hands_hip.h: ev2h_esim_step)")
+        self.rows = None
+        self._annotation_frame_host = None
+
+    # ------------------------------------------------------------------------------------------------------------------ the state
+    def begin(self) -> None:
+        dev, F, H, W = self.device, self.chunk, self.h, self.w
+        self.rows = torch.empty(self.capacity, 6, device=dev, dtype=torch.float64)
+        self.mem_frame = torch.full((H, W), initial_mem_value(), device=dev, dtype=torch.float64)
+        self.prev_log = torch.zeros(H, W, device=dev, dtype=torch.float64)
+        self._counters = torch.zeros(_STATE_WORDS + self.max_annotations, device=dev, dtype=torch.int32)
+        self.state = self._counters[:_STATE_WORDS].view(torch.int64)           # frames, rows, annotations, status, sort frame, sort count
+        self.state[4] = -1
+        self.annotation_frame = self._counters[_STATE_WORDS:]
+        self._scratch = torch.empty(self.scratch_bytes, device=dev, dtype=torch.uint8)
+        self._rgb = torch.empty(F, H, W, 3, device=dev, dtype=torch.uint8)
+        if self.frames is not None:                                             # what `step` writes on its way to the events
+            self._verts = torch.empty(2, F, 778, 3, device=dev, dtype=torch.float32)
+            self._joints = torch.empty(2, F, 21, 3, device=dev, dtype=torch.float32)
+            self._frame = torch.empty(F, H, W, 3, device=dev, dtype=torch.uint8)
+            self._face_id = torch.empty(F, H, W, device=dev, dtype=torch.int32)
+        self._behind = torch.tensor([0.0, 0.0, -1.0], device=dev, dtype=torch.float32)    # a hand that is not present: behind the camera
+        self._annotation_frame_host = None
+        self.n_frames = 0
+
+    def _begun(self) -> None:
+        if self.rows is None:
+            raise RuntimeError("call begin() first")
+
+    # ------------------------------------------------------------------------------------------------------------------ the steps
+    def step_images(self, rgb, face_id=None, labels=None) -> None:
+        """rgb uint8 [F, H, W, 3] on the device, F <= chunk; labels from face_id int32 [F, H, W] (-1 -> 0, < nf -> 1, else 2) or a
+        uint8 [F, H, W] label map taken as it is; neither: label 0."""
+        self._begun()
+        if not torch.is_tensor(rgb) or rgb.dim() != 4:
+            raise ValueError(f"rgb must be a uint8 tensor [F, {self.h}, {self.w}, 3] on {self.device}")
+        F = int(rgb.shape[0])
+        if not 1 <= F <= self.chunk:
+            raise ValueError(f"a step takes 1 .. {self.chunk} frames, got {F}")
+        _dev_tensor(rgb, "rgb", torch.uint8, (F, self.h, self.w, 3), self.device)
+        if face_id is not None and labels is not None:
+            raise ValueError("give face_id or labels, not both")
+        nf = 0
+        if face_id is not None:
+            _dev_tensor(face_id, "face_id", torch.int32, (F, self.h, self.w), self.device)
+            nf = self.nf if self.frames is not None else 0
+            if nf < 1:
+                raise ValueError("labels from face_id need the hands' faces (hands=None): give a label map")
+        if labels is not None:
+            _dev_tensor(labels, "labels", torch.uint8, (F, self.h, self.w), self.device)
+        _lib.check(_lib.lib().ev2h_esim_step(rgb.data_ptr(), F, self.w, self.h, _lib.ptr(face_id), nf, _lib.ptr(labels), self.table.data_ptr(),
+                                             self.tp, self.tn, self.eps, self.fps, self.mode, self.max_pp, self.mepf, self.mem_frame.data_ptr(),
+                                             self.prev_log.data_ptr(), self.state.data_ptr(), self.rows.data_ptr(), self.capacity,
+                                             self.annotation_frame.data_ptr(), self.max_annotations, self._scratch.data_ptr(),
+                                             self._scratch.numel(), _lib.stream_handle()), "ev2h_esim_step")
+        self.n_frames += F
+
+    def render(self, params_left, params_right, present=None):
+        """-> (rgb uint8 [F, H, W, 3], the render's frame, face_id): what `step` feeds the generator, views of buffers allocated in
+        `begin` that the next call overwrites"""
+        self._begun()
+        if self.frames is None:
+            raise RuntimeError("EventSimulatorS was built without hands: only step_images is available")
+        verts = []
+        F = int(params_left.shape[0]) if torch.is_tensor(params_left) and params_left.dim() == 2 else 0
+        if not 1 <= F <= self.chunk:
+            raise ValueError(f"a step takes 1 .. {self.chunk} frames")
+        if present is not None:
+            _dev_tensor(present, "present", torch.bool, (F, 2), self.device)
+        for h, (side, prm) in enumerate((("left", params_left), ("right", params_right))):
+            hand = self.hands[side]
+            _dev_tensor(prm, f"params_{side}", torch.float32, (F, 16 + hand.ncomps), self.device)
+            v = self._verts[h, :F]
+            c = hand.consts()
+            _lib.check(_lib.lib().ev2h_mano(C.byref(c), prm.data_ptr(), prm.shape[1], F, v.data_ptr(), 0, self._joints[h, :F].data_ptr(), 0,
+                                            _lib.stream_handle()), "ev2h_mano")
+            if present is not None:
+                torch.where(present[:, h, None, None], v, self._behind, out=v)
+            verts.append(v)
+        frame, _, face_id = self.frames.render(verts[0], verts[1], out=(self._frame[:F], None, self._face_id[:F]))
+        rgb = self._rgb[:F]
+        r, g, b = self.hand_color
+        _lib.check(_lib.lib().ev2h_esim_compose(frame.data_ptr(), face_id.data_ptr(), self.background.data_ptr(), F, self.w, self.h, r, g, b,
+                                                rgb.data_ptr(), _lib.stream_handle()), "ev2h_esim_compose")
+        return rgb, frame, face_id
+
+    def step(self, params_left, params_right, present=None) -> None:
+        """params_* float32 [F, 16 + K] (global_orient | hand_pose | betas | transl, camera space), F <= chunk; present bool [F, 2]:
+        False drops that hand from that frame (it is moved behind the camera)."""
+        rgb, _, face_id = self.render(params_left, params_right, present)
+        self.step_images(rgb, face_id=face_id)
+
+    # ------------------------------------------------------------------------------------------------------------------ the end
+    def read_status(self) -> dict:
+        """the one host read: the counters and annotation_frame"""
+        self._begun()
+        host = self._counters.cpu().numpy()
+        st = host[:_STATE_WORDS].view(np.int64)
+        n_ann = int(st[2])
+        self._annotation_frame_host = host[_STATE_WORDS:_STATE_WORDS + min(n_ann, self.max_annotations)].copy()
+        return {"n_frames": int(st[0]), "n_rows": int(st[1]), "n_annotations": n_ann, "status": int(st[3]), "sort_frame": int(st[4]),
+                "sort_count": int(st[5]), "annotation_frame": self._annotation_frame_host}
+
+    def check(self, info: dict | None = None) -> dict:
+        """raises on any status bit (reads the counters unless `info` = read_status() is given)"""
+        info = self.read_status() if info is None else info
+        s = info["status"]
+        if s & _lib.ESIM_OVER_SORT:
+            raise RuntimeError(f"frame {info['sort_frame']} holds {info['sort_count']} events, more than max_events_per_frame = {self.mepf}: "
+                               "its rows were not written (there is no fallback order)")
+        if s & _lib.ESIM_LOOP_BOUND:
+            raise RuntimeError(f"a pixel reached max_per_pixel = {self.max_pp} events in one frame")
+        if s & _lib.ESIM_OVER_CAPACITY:
+            raise RuntimeError(f"{info['n_rows']} rows and {info['n_annotations']} annotations were counted, capacity = {self.capacity} rows and "
+                               f"max_annotations = {self.max_annotations}")
+        return info
+
+    def finish(self):
+        """-> (EventTableS over the written rows, info: n_rows, n_annotations, annotation_frame, status, n_frames); raises on any status bit"""
+        info = self.check()
+        if info["n_rows"] < 1:
+            raise RuntimeError("the sequence gave no event")
+        return EventTableS(self.device, self.rows[:info["n_rows"]]), info
+
+    def annotation_table(self, params_left, params_right) -> torch.Tensor:
+        """float32 [A, 2, 16 + K] on the device: the rows of the frames that got an annotation (after finish / read_status), hand 0 =
+        left -- evaluate.annotation_table's layout (global_orient | hand_pose | shape | trans), for TrainingBatcherS(annotation_table=...)"""
+        if self._annotation_frame_host is None:
+            raise RuntimeError("call finish() first")
+        idx = torch.from_numpy(self._annotation_frame_host.astype(np.int64)).to(self.device)
+        if idx.numel() and int(self._annotation_frame_host.max()) >= min(params_left.shape[0], params_right.shape[0]):
+            raise ValueError("the parameter rows are fewer than the simulated frames")
+        return torch.stack([params_left.to(self.device)[idx], params_right.to(self.device)[idx]], 1).to(torch.float32).contiguous()
+
+
+def simulate(device, hands, params_left, params_right, present=None, **kw):
+    """begin / step per chunk / finish for whole sequences params_* float32 [T, 16 + K] -> (EventTableS, info), as `finish` returns"""
+    sim = EventSimulatorS(device, hands, **kw)
+    sim.begin()
+    T = int(params_left.shape[0])
+    for at in range(0, T, sim.chunk):
+        sl = slice(at, min(at + sim.chunk, T))
+        sim.step(params_left[sl].contiguous(), params_right[sl].contiguous(), None if present is None else present[sl].contiguous())
+    return sim.finish()

@@ -39,7 +39,8 @@ import torch
 
 from . import _lib
 from ._lib import _dev_tensor
-from .evaluate import annotation_flags, annotation_table
+from .evaluate import annotation_flags
+from .evaluate import annotation_table as _annotation_table          # (TrainingBatcherS takes a keyword of that name)
 from .events import _NO_WINDOW, OUTPUT_HEIGHT, OUTPUT_WIDTH, EventTableS, EventWindowBuilder, EventWindowBuilderS
 from .stream import EventStream, load_recording
 
@@ -47,7 +48,9 @@ from .stream import EventStream, load_recording
 class TrainingBatcherS:
     """annotations: the sequence's annotation dict (evaluate.annotation_table's input), uploaded once with the `valid` / `handedness`
     the reference attaches (evaluate.annotation_flags; reference_quirks: a one-hand annotation clears the valid of both hands, as
-    upstream's shared dict does).  augment=False gives the validation loader's items.  Every buffer a batch is written into is
+    upstream's shared dict does); or annotations=None and annotation_table=(table, flags): the device tensors themselves, float32
+    [A, 2, 16 + n_pose] (evaluate.annotation_table's layout) and int32 [A, 2, 2] (evaluate.annotation_flags'), such as
+    EventSimulatorS.annotation_table gives.  augment=False gives the validation loader's items.  Every buffer a batch is written into is
     allocated in `begin`; the dict `batch` returns holds views of them, overwritten by the next call.
 
     `status` (device int32 [1], 2**31-1 while all is well) receives the smallest id of a window that could not be built: empty, more
@@ -55,7 +58,7 @@ class TrainingBatcherS:
     it, which synchronises; nothing else here does."""
 
     def __init__(self, device, annotations, *, n_pose: int = 6, seed: int = 0, batch: int = 8, n_events: int = 2048, augment: bool = True,
-                 reference_quirks: bool = True, cap: int = 4096, width: int = OUTPUT_WIDTH, height: int = OUTPUT_HEIGHT):
+                 reference_quirks: bool = True, cap: int = 4096, width: int = OUTPUT_WIDTH, height: int = OUTPUT_HEIGHT, annotation_table=None):
         self.device = torch.zeros(0, device=device).device
         if self.device.type != "cuda":
             raise RuntimeError("TrainingBatcherS runs on the GPU only (there is no CPU fallback)")
@@ -63,8 +66,19 @@ class TrainingBatcherS:
             raise ValueError("n_pose must be 1 .. 45, batch positive and seed an unsigned 64-bit integer")
         self.n_pose, self.seed, self.max_batch, self.augment = int(n_pose), int(seed), int(batch), bool(augment)
         self.builder = EventWindowBuilderS(self.device, n_events, width, height, cap)
-        self.annotation_table = torch.from_numpy(annotation_table(annotations, self.n_pose)).to(self.device).reshape(-1, 2 * (16 + self.n_pose))
-        self.annotation_flags = torch.from_numpy(annotation_flags(annotations, reference_quirks)).to(self.device).reshape(-1, 4)
+        if annotation_table is not None:
+            if annotations is not None:
+                raise ValueError("give `annotations` or `annotation_table`, not both")
+            table, flags = annotation_table
+            A = int(table.shape[0]) if torch.is_tensor(table) and table.dim() == 3 else 0
+            _dev_tensor(table, "annotation_table[0]", torch.float32, (A, 2, 16 + self.n_pose), self.device)
+            _dev_tensor(flags, "annotation_table[1]", torch.int32, (A, 2, 2), self.device)
+            if A < 1:
+                raise ValueError("annotation_table holds no annotation")
+            self.annotation_table, self.annotation_flags = table.reshape(A, 2 * (16 + self.n_pose)), flags.reshape(A, 4)
+        else:
+            self.annotation_table = torch.from_numpy(_annotation_table(annotations, self.n_pose)).to(self.device).reshape(-1, 2 * (16 + self.n_pose))
+            self.annotation_flags = torch.from_numpy(annotation_flags(annotations, reference_quirks)).to(self.device).reshape(-1, 4)
         self.n_annotations = int(self.annotation_table.shape[0])
         self.table = None
 

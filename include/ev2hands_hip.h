@@ -883,6 +883,69 @@ int ev2h_render_hands(const float* verts_left, const float* verts_right, size_t 
                       uint8_t* frame, int frame_width, int render_x0, int clear_x0, int clear_width,
                       float* depth, int32_t* face_id, void* scratch, size_t scratch_bytes, ev2h_stream_t stream);
 
+/* ---- the Ev2Hands-S event simulator (HandSimulator/color_event_simulator.py:112-191, main.py:71-87, stich_mp.py:39-42) ------- */
+/* uint8 RGB frames -> rows [E][6] float64 (x, y, t, p, annotation index, label), the `event` dataset of the synthetic set, appended
+ * to a caller-owned table (csrc/esim.hip).  One call consumes a chunk of n_frames frames rgb [n_frames][height][width][3]; any split
+ * of a sequence into calls gives the same rows, byte for byte.
+ *
+ * State, caller-owned and on the device: mem_frame / prev_log [height][width] float64 (the reference starts mem_frame at
+ * log((159/255)**2.2 + 0.01); prev_log is only read by the interpolated timestamps), and state int64[8]:
+ *   [EV2H_ESIM_STATE_FRAMES] frames consumed, [_ROWS] rows counted (the TRUE total, also beyond `capacity`), [_ANNOTATIONS]
+ *   annotations given, [_STATUS] the OR of the EV2H_ESIM_* status bits below, [_SORT_FRAME] / [_SORT_COUNT] the first global frame
+ *   with more events than max_events_per_frame and its count (frame -1: none; the caller starts it at -1, the rest at 0).
+ *
+ * The rule.  log_table [256] float64 on the device: the log value of a byte, the reference's own expression evaluated on the host
+ *   np.log(((np.arange(256).astype(np.uint8).astype(np.float32) / 255) ** 2.2).astype(np.float64) + 1e-4).
+ * L(y, x) = log_table[rgb[y][x][channel]], channel = R at (even y, even x), G at (even, odd) and (odd, even), B at (odd, odd).  Per
+ * frame and pixel, in float64:  while (L - mem > tp - eps) { +1 event; mem += tp; }  while (L - mem < -tn + eps) { -1 event; mem -=
+ * tn; }.  Global frame 0 updates mem_frame and emits nothing.  Each loop ends after max_per_pixel (1 .. 127) rounds; one that ends
+ * that way with its condition still true sets EV2H_ESIM_LOOP_BOUND.  A frame's annotation index is the number of earlier frames
+ * that emitted at least one event (a frame without events takes no annotation); annotation_frame[a] receives the global frame of
+ * annotation a (a >= annotation_capacity: not written, EV2H_ESIM_OVER_CAPACITY).  label: labels [n_frames][height][width] uint8 taken
+ * as it is, or from face_id [n_frames][height][width] int32: -1 -> 0, < nf -> 1 (left), else 2 (right); neither map: 0; both:
+ * EV2H_ERR_ARG.  Rows at or beyond `capacity` are counted, not written (EV2H_ESIM_OVER_CAPACITY).
+ *
+ * mode EV2H_ESIM_FRAME: t = the global frame number, rows in (frame, y, x, emission) order: the reference's ColorEventSimulator, bit
+ *   for bit (tests/golden/events_esim_frames_*.npz).  EV2H_ESIM_FRAME_SCALED: the same with t = frame * 1e9 / fps.
+ * mode EV2H_ESIM_INTERPOLATED: ESIM's linear crossing times on this memory frame -- the project's own statement, parity with
+ *   esim_torch unpinned.  Event k = 1 .. n of a pixel in frame f, with mem the memory value before the frame, L0 the previous
+ *   frame's log value and L1 this one's:  level = mem + k tp (mem - k tn),  frac = (level - L0) / (L1 - L0) clamped to [0, 1] (a
+ *   NaN counts as 0),  t_ns = (int64)(((f - 1) + frac) * (1e9 / fps)), truncated; a frame's rows are ordered by (t_ns, y, x, k).
+ *   A frame with more than max_events_per_frame (1 .. 8192) events sets EV2H_ESIM_OVER_SORT and gets NO rows: its rows are counted
+ *   and the rows of later frames keep their offsets, so the table then holds a gap of that many rows that nothing wrote -- a table
+ *   with this bit set is not to be used (EventSimulatorS.finish raises).  1e9 / fps <= 2^33.
+ *
+ * Three passes, no atomics: the same call gives the same bytes.  scratch: device, 16-byte aligned, ev2h_esim_scratch_bytes(...)
+ * bytes (0: arguments out of range), used on `stream` only.  Allocates nothing, does not synchronise, reads nothing back.
+ * EV2H_ERR_ARG before any launch: a null pointer, n_frames outside 1 .. 4096, width * height outside 1 .. 2^22, tp <= 2 eps or
+ * tn <= 2 eps (then both loops could run for one pixel), eps < 0, a non-finite threshold, a mode outside 0 .. 2, fps <= 0 where it is
+ * used, max_per_pixel outside 1 .. 127, capacity or annotation_capacity < 1, n_frames * width * height * max_per_pixel >= 2^31,
+ * a scratch that is too small or misaligned. */
+#define EV2H_ESIM_FRAME 0
+#define EV2H_ESIM_FRAME_SCALED 1
+#define EV2H_ESIM_INTERPOLATED 2
+#define EV2H_ESIM_OVER_CAPACITY 1
+#define EV2H_ESIM_LOOP_BOUND 2
+#define EV2H_ESIM_OVER_SORT 4
+#define EV2H_ESIM_STATE_FRAMES 0
+#define EV2H_ESIM_STATE_ROWS 1
+#define EV2H_ESIM_STATE_ANNOTATIONS 2
+#define EV2H_ESIM_STATE_STATUS 3
+#define EV2H_ESIM_STATE_SORT_FRAME 4
+#define EV2H_ESIM_STATE_SORT_COUNT 5
+size_t ev2h_esim_scratch_bytes(int n_frames, int width, int height, int mode, int max_events_per_frame);
+int ev2h_esim_step(const uint8_t* rgb, int n_frames, int width, int height, const int32_t* face_id, int nf, const uint8_t* labels,
+                   const double* log_table, double threshold_pos, double threshold_neg, double eps, double fps, int mode,
+                   int max_per_pixel, int max_events_per_frame, double* mem_frame, double* prev_log, int64_t* state, double* rows,
+                   int capacity, int32_t* annotation_frame, int annotation_capacity, void* scratch, size_t scratch_bytes,
+                   ev2h_stream_t stream);
+/* The frame the simulator sees for a rendered chunk: frame [n_frames][height][width][3] uint8 as ev2h_render_hands writes it (its
+ * intensity I is byte 2) and face_id; a pixel with face_id >= 0 gets (uint8)(int)((float)I / 255.0f * colour + 0.5f) per channel
+ * (float32, one rounding per operation), every other pixel background [height][width][3].  rgb [n_frames][height][width][3].
+ * The project's own colouring: the reference renders UV textures under random lights over background images. */
+int ev2h_esim_compose(const uint8_t* frame, const int32_t* face_id, const uint8_t* background, int n_frames, int width, int height,
+                      int red, int green, int blue, uint8_t* rgb, ev2h_stream_t stream);
+
 /* ---- whole path -------------------------------------------------------------------------------------- */
 typedef struct ev2h_sa_branch {
     const float* W1x; const float* W2; const float* b2; const float* W3; const float* b3;
