@@ -101,7 +101,8 @@ W_EQUALIZED, W_UNEQUALIZED_OK = 1, 2
 # (ev2h_event_window_build_ranges_flip, ev2h_finetune_resolve, ev2h_finetune_targets), and for the gradient exports (ev2h_mano_backward,
 # ev2h_segmentation_score_backward, ev2h_loss_terms_backward, ev2h_collision_penalty_backward), and for the test hooks (ev2h_dbg_*),
 # and for the fitting exports (ev2h_mano_joints_jacobian, ev2h_mano_fit, ev2h_mano_fit_opts_size), and for the event simulator
-# (ev2h_esim_scratch_bytes, ev2h_esim_step, ev2h_esim_compose).
+# (ev2h_esim_scratch_bytes, ev2h_esim_step, ev2h_esim_compose), and for the pose track (ev2h_pose_track_prepare, ev2h_pose_track_rows,
+# ev2h_pose_track_hand_size).
 ABI_VERSION = 8     # 8: EV2H_PREC_F16 (one fp16 plane with f16x2's range machinery); 3: F16X2 range records; 4: ev2h_fp_mlp, ev2h_weights.fp1m; 5: window strides of the outputs; 6: ev2h_pack_weights, ev2h_weights.flags; 7: ev2h_sa_desc.xyz_out
 
 PREC = {"f32": 0, "bf16": 1, "f16x2": 2, "bf16x3": 3, "f16": 4}
@@ -118,6 +119,12 @@ class ManoFitOpts(C.Structure):
                 ("max_iters", C.c_int32), ("free_mask", C.c_int32)]
 
 
+class PoseTrackHand(C.Structure):
+    _fields_ = [("keys", vp), ("quat", vp), ("rel", vp), ("coef", vp), ("inv_comps", vp), ("J_template", vp), ("J_shape", vp),
+                ("n_keys", C.c_int32), ("ncomps", C.c_int32)]
+
+
+POSE_TRACK_KEY, POSE_TRACK_COEF, POSE_TRACK_PARTS = 61, 14, 112      # EV2H_POSE_TRACK_*
 ESIM_MODES = {"frame": 0, "scaled": 1, "interpolated": 2}      # EV2H_ESIM_FRAME, _FRAME_SCALED, _INTERPOLATED
 ESIM_OVER_CAPACITY, ESIM_LOOP_BOUND, ESIM_OVER_SORT = 1, 2, 4     # the status bits of ev2h_esim_step's state[3]
 FIT_GROUPS = ("global_orient", "hand_pose", "betas", "transl")      # bits 0..3 of ev2h_mano_fit_opts.free_mask
@@ -149,6 +156,7 @@ EXPORTS = [
     "ev2h_mano_backward", "ev2h_segmentation_score_backward", "ev2h_loss_terms_backward", "ev2h_collision_penalty_backward",
     "ev2h_mano_joints_jacobian", "ev2h_mano_fit", "ev2h_mano_fit_opts_size",
     "ev2h_esim_scratch_bytes", "ev2h_esim_step", "ev2h_esim_compose",
+    "ev2h_pose_track_prepare", "ev2h_pose_track_rows", "ev2h_pose_track_hand_size",
     # test hooks, not part of the stable interface (include/ev2hands_hip.h: "Test hooks"; ev2hands_amd/ops.py: *_rows16, dense_zsum, ...)
     "ev2h_dbg_fp_mlp_rows16", "ev2h_dbg_gemm_zsum_supported", "ev2h_dbg_gemm_zsum", "ev2h_dbg_attn_simfold_partials", "ev2h_dbg_attn_context_rows16",
 ]
@@ -262,6 +270,10 @@ def lib() -> C.CDLL:
     L.ev2h_esim_step.argtypes = [vp, ci, ci, ci, vp, ci, vp, vp, C.c_double, C.c_double, C.c_double, C.c_double, ci, ci, ci, vp, vp, vp, vp,
                                  ci, vp, ci, vp, C.c_size_t, vp]
     L.ev2h_esim_compose.argtypes = [vp, vp, vp, ci, ci, ci, ci, ci, ci, vp, vp]
+    L.ev2h_pose_track_hand_size.restype = C.c_size_t
+    L.ev2h_pose_track_hand_size.argtypes = []
+    L.ev2h_pose_track_prepare.argtypes = [vp, ci, vp, vp, vp, vp]
+    L.ev2h_pose_track_rows.argtypes = [C.POINTER(PoseTrackHand), ci, ci, ci, vp, C.POINTER(C.c_double), vp, vp, ci, vp, vp, vp]
     L.ev2h_dbg_fp_mlp_rows16.argtypes = [C.POINTER(FpDesc), ci, ci, vp, C.c_float, C.c_float, vp]
     L.ev2h_dbg_gemm_zsum_supported.argtypes = [C.POINTER(GemmDesc)]
     L.ev2h_dbg_gemm_zsum.argtypes = [C.POINTER(GemmDesc), vp, vp, ci, vp, vp]
@@ -303,6 +315,8 @@ def lib() -> C.CDLL:
         raise Ev2hError(f"struct layout mismatch between ev2hands_hip.h and _lib.py: {list(sizes)} vs {mine}")
     if L.ev2h_mano_fit_opts_size() != C.sizeof(ManoFitOpts):
         raise Ev2hError(f"struct layout mismatch between ev2hands_hip.h and _lib.py: ev2h_mano_fit_opts {L.ev2h_mano_fit_opts_size()} vs {C.sizeof(ManoFitOpts)}")
+    if L.ev2h_pose_track_hand_size() != C.sizeof(PoseTrackHand):
+        raise Ev2hError(f"struct layout mismatch between ev2hands_hip.h and _lib.py: ev2h_pose_track_hand {L.ev2h_pose_track_hand_size()} vs {C.sizeof(PoseTrackHand)}")
     if L.ev2h_abi_version() != ABI_VERSION:
         raise Ev2hError(f"ABI version mismatch: library {L.ev2h_abi_version()}, binding {ABI_VERSION}")
     _lib = L

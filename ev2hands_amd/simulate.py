@@ -6,6 +6,8 @@ main.py, renderer.py, color_event_simulator.py, stich_mp.py) without its files.
     sim.step(params_left, params_right)                  # float32 [F, 16 + K] each: MANO -> render -> compose -> events
     table, info = sim.finish()                           # the ONE host read: an EventTableS over the written rows
     batcher = TrainingBatcherS(device, None, annotation_table=(sim.annotation_table(params_left, params_right), flags))
+    sim.step_track(track, f0, f1)                        # the same from a PoseTrack (pose_track.py): keyframes -> rows on the device
+    table, info = simulate_track(device, net.hands, track); sim.annotation_table_track(track)
 
 What is PINNED: `step_images` with timestamps="frame" is the reference's ColorEventSimulator (its CPU driver) bit for bit -- events,
 their order, the memory frame, the annotation indices of main.py:71-75 / stich_mp.py:40 and the labels of main.py:87
@@ -19,8 +21,8 @@ render (csrc/render.hip, itself unpinned against pyrender) coloured with one `ha
 UV textures, random lights and background images.  The labels are the render's own face_id (0 background, 1 left, 2 right), which is
 what the reference's segmentation render encodes.
 
-NOT provided: UV textures, lights, background image sets, the InterHand readers, pose interpolation (augmentations.interpolate_sequence),
-camera transforms of the parameter rows (the rows are camera-space, as camera_hand_info is) and .h5 / pickle writing.
+NOT provided: UV textures, lights, background image sets, the InterHand readers and .h5 / pickle writing.  The rows `step` takes are
+camera-space, as camera_hand_info is; pose_track.PoseTrack makes them from keyframes (interpolation, AA -> PCA, camera transform).
 
 Every buffer is allocated in `begin`: `step_images` and `step` synchronise nothing, allocate nothing and read nothing back; `finish`
 reads the counters once.
@@ -113,6 +115,11 @@ class EventSimulatorS:
             self._joints = torch.empty(2, F, 21, 3, device=dev, dtype=torch.float32)
             self._frame = torch.empty(F, H, W, 3, device=dev, dtype=torch.uint8)
             self._face_id = torch.empty(F, H, W, device=dev, dtype=torch.int32)
+            self._track_rows = None                                             # what `step_track` has the track write
+            if hasattr(self.hands["left"], "ncomps"):                           # (hands that hold faces only can render vertices, not rows)
+                P = 16 + self.hands["left"].ncomps
+                self._track_rows = (torch.empty(F, P, device=dev, dtype=torch.float32), torch.empty(F, P, device=dev, dtype=torch.float32),
+                                    torch.empty(F, 2, device=dev, dtype=torch.bool))
         self._behind = torch.tensor([0.0, 0.0, -1.0], device=dev, dtype=torch.float32)    # a hand that is not present: behind the camera
         self._annotation_frame_host = None
         self.n_frames = 0
@@ -184,6 +191,20 @@ class EventSimulatorS:
         rgb, _, face_id = self.render(params_left, params_right, present)
         self.step_images(rgb, face_id=face_id)
 
+    def step_track(self, track, f0: int, f1: int) -> None:
+        """`step` on the frames [f0, f1) of a pose_track.PoseTrack, f1 - f0 <= chunk: the track writes its rows and `present` into buffers
+        allocated in `begin`; no row crosses from the host and nothing is read back"""
+        self._begun()
+        if self.frames is None or self._track_rows is None:
+            raise RuntimeError("EventSimulatorS was built without MANO layers: step_track needs them")
+        F = int(f1) - int(f0)
+        if not 1 <= F <= self.chunk:
+            raise ValueError(f"a step takes 1 .. {self.chunk} frames, got {F}")
+        if track.device != self.device or track.width != self._track_rows[0].shape[1]:
+            raise ValueError(f"the track must live on {self.device} and give rows of {self._track_rows[0].shape[1]} values")
+        pl, pr, present = track.rows(f0, f1, out=tuple(t[:F] for t in self._track_rows))
+        self.step(pl, pr, present)
+
     # ------------------------------------------------------------------------------------------------------------------ the end
     def read_status(self) -> dict:
         """the one host read: the counters and annotation_frame"""
@@ -225,6 +246,29 @@ class EventSimulatorS:
         if idx.numel() and int(self._annotation_frame_host.max()) >= min(params_left.shape[0], params_right.shape[0]):
             raise ValueError("the parameter rows are fewer than the simulated frames")
         return torch.stack([params_left.to(self.device)[idx], params_right.to(self.device)[idx]], 1).to(torch.float32).contiguous()
+
+
+    def annotation_table_track(self, track) -> torch.Tensor:
+        """`annotation_table` for a sequence that came from a pose_track.PoseTrack (after finish / read_status): the track's rows of
+        the frames in annotation_frame, computed on the device from the device's own copy of the indices -- no host read"""
+        if self._annotation_frame_host is None:
+            raise RuntimeError("call finish() first")
+        A = len(self._annotation_frame_host)
+        if A == 0:
+            return torch.empty(0, 2, track.width, device=self.device, dtype=torch.float32)
+        if int(self._annotation_frame_host.max()) >= len(track):
+            raise ValueError("the track is shorter than the simulated frames")
+        pl, pr, _ = track.rows_at(self.annotation_frame[:A])
+        return torch.stack([pl, pr], 1)
+
+
+def simulate_track(device, hands, track, **kw):
+    """begin / step_track per chunk / finish for a whole pose_track.PoseTrack -> (EventTableS, info), as `finish` returns"""
+    sim = EventSimulatorS(device, hands, **kw)
+    sim.begin()
+    for at in range(0, len(track), sim.chunk):
+        sim.step_track(track, at, min(at + sim.chunk, len(track)))
+    return sim.finish()
 
 
 def simulate(device, hands, params_left, params_right, present=None, **kw):

@@ -946,6 +946,65 @@ int ev2h_esim_step(const uint8_t* rgb, int n_frames, int width, int height, cons
 int ev2h_esim_compose(const uint8_t* frame, const int32_t* face_id, const uint8_t* background, int n_frames, int width, int height,
                       int red, int green, int blue, uint8_t* rgb, ev2h_stream_t stream);
 
+/* ---- MANO keyframes -> the simulator's pose rows (csrc/pose_track.hip; HandSimulator/dataset/utils.py:11-113, interhand.py:69-158) ----
+ * A hand's track is L keyframe rows keys [L][61] float64 = pose(48: 16 axis-angle joints) | shape(10) | trans(3) at the uniform knots
+ * x_i = i.  float64 throughout; no atomics, every sum in index order: the same call gives the same bytes.
+ *
+ * ev2h_pose_track_prepare, once per track and hand (what scipy's Slerp.__init__ and the cubic interp1d set up):
+ *   quat [L][16][4] (x, y, z, w): scipy's Rotation.from_rotvec -- a = |v|, (x, y, z) = s v, w = cos(a / 2) with s = sin(a / 2) / a,
+ *     or 0.5 - a^2 / 48 + a^4 / 3840 at a <= 1e-3;
+ *   rel [L - 1][16][3]: the rotation vector of normalise(conj(q_i) (x) q_{i+1}) (Hamilton product), scipy's as_rotvec -- the sign
+ *     with w >= 0, angle = 2 atan2(|v|, w), v * angle / sin(angle / 2), or v * (2 + angle^2 / 12 + 7 angle^4 / 2880) at angle <= 1e-3;
+ *   coef [L][14]: columns 0..12 the second derivatives M_i of the NOT-A-KNOT cubic spline through the 13 scalar channels (keys
+ *     columns 48..60), column 13 the elimination's own pivots (scratch).  6 M_1 = d_1 and 6 M_{L-2} = d_{L-2} with
+ *     d_i = 6 (y_{i-1} - 2 y_i + y_{i+1}); M_{i-1} + 4 M_i + M_{i+1} = d_i for i = 2 .. L - 3, by sequential elimination (one lane per
+ *     channel); M_0 = 2 M_1 - M_2, M_{L-1} = 2 M_{L-2} - M_{L-3}.  L = 4: the two end conditions coincide, the interior system is
+ *     empty and the spline is the one cubic through the four points.  The spline is unique, so this is scipy's function up to rounding.
+ *   EV2H_ERR_ARG before any device call: a null pointer, L outside 4..65536.
+ *
+ * ev2h_pose_track_rows: the rows of the frames [f0, f1) of an n-frame track (frame_index NULL), or of the f1 - f0 frames
+ * frame_index[k] (device int32; an index outside 0..n-1 gives present = 0 and a zero row), both hands in one launch, one wavefront
+ * per (frame, hand).  For frame i and a hand with L keyframes:
+ *   x = i * ((L - 1) / (double)(n - 1)), x = L - 1 for i = n - 1 (np.linspace(0, L - 1, n));
+ *   ind = clamp(ceil(x) - 1, 0, L - 2), alpha = x - ind (np.searchsorted(side='left') - 1 with Slerp's t == times[0] fix);
+ *   joint j: rotvec(normalise(quat[ind][j] (x) from_rotvec(alpha * rel[ind][j]))), the conventions above;
+ *   channel c: with b = 1 - alpha: b y_ind + alpha y_{ind+1} + ((b^3 - b) M_ind + (alpha^3 - alpha) M_{ind+1}) / 6;
+ *   pca[j] = sum_{i = 0..44, in order} aa[3 + i] * inv_comps[i][j] (inv_comps [45][45]: the float32 inverse of hands_components, widened);
+ *   camera (cam != NULL: HOST float64[12] = R [3][3] row-major, a rotation, then t in MILLIMETRES):
+ *     global_orient' = the vector the layer turns into R * (the layer's rotation of global_orient): the layer's map is the quaternion
+ *       normalise(cos(g / 2), sin(g / 2) theta / g) with g = |theta + 1e-8| (ev2h_mano_rotations), so both the map and its inverse
+ *       are taken with that offset (the inverse: the exact logarithm, then two steps s <- s + (angle wanted - angle the layer gives
+ *       for s * axis)); the product is formed on quaternions (R's by Shepperd's method on the host), which is well conditioned up to
+ *       and including pi, where the sign with w >= 0 is kept;
+ *     transl' = R transl + t / 1000 + R J0 - J0, J0 = J_template[0] + sum_k betas_k J_shape[k][0..2] (k in order; the layer turns
+ *       the hand about that joint, so the layer's vertices and joints of the new row are R * (the old ones) + t / 1000).
+ *   rows_h [F][ld_rows] float32 = global_orient(') | pca[0 .. ncomps) | shape | transl('), each value rounded once from float64;
+ *   present [F][2] bytes 0 / 1; parts (may be NULL) [F][2][EV2H_POSE_TRACK_PARTS] float64, before rounding: pose 48 (axis-angle, before
+ *   the camera) | pca 45 | shape 10 | trans 3 (before the camera) | global_orient' 3 | transl' 3 (the same as before without a camera).
+ *   A hand with n_keys == 0 is absent: present = 0 and zero rows in every frame (its other fields are not read).
+ * Frame i's bytes depend on i, n and the keyframes only, whatever the range or the chunking.
+ *   EV2H_ERR_ARG before any device call: a null hands / present, n < 2, a range outside 0 <= f0 < f1 <= n (frame_index NULL; else
+ *   f0 < f1), n_keys neither 0 nor 4..65536, ncomps outside 1..45, ld_rows < 16 + ncomps, a null field or rows pointer of a present
+ *   hand, both hands absent, a cam that is not finite.  One launch, no host synchronisation, capturable. */
+#define EV2H_POSE_TRACK_KEY 61
+#define EV2H_POSE_TRACK_COEF 14
+#define EV2H_POSE_TRACK_PARTS 112
+typedef struct ev2h_pose_track_hand {
+    const double* keys;          /* [n_keys][61]                                                    */
+    const double* quat;          /* [n_keys][16][4]      ev2h_pose_track_prepare's outputs           */
+    const double* rel;           /* [n_keys - 1][16][3]                                             */
+    const double* coef;          /* [n_keys][14]                                                    */
+    const double* inv_comps;     /* [45][45]                                                        */
+    const float* J_template;     /* ev2h_mano_consts.J_template / J_shape (camera only; else may be NULL) */
+    const float* J_shape;
+    int32_t n_keys;              /* 0: the hand is absent                                           */
+    int32_t ncomps;              /* 1..45: the coefficients a row takes                             */
+} ev2h_pose_track_hand;
+size_t ev2h_pose_track_hand_size(void);    /* sizeof(ev2h_pose_track_hand), for the binding's layout check */
+int ev2h_pose_track_prepare(const double* keys, int n_keys, double* quat, double* rel, double* coef, ev2h_stream_t stream);
+int ev2h_pose_track_rows(const ev2h_pose_track_hand* hands, int n, int f0, int f1, const int32_t* frame_index, const double* cam,
+                         float* rows_left, float* rows_right, int ld_rows, uint8_t* present, double* parts, ev2h_stream_t stream);
+
 /* ---- whole path -------------------------------------------------------------------------------------- */
 typedef struct ev2h_sa_branch {
     const float* W1x; const float* W2; const float* b2; const float* W3; const float* b3;
