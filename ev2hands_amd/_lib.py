@@ -100,7 +100,8 @@ W_EQUALIZED, W_UNEQUALIZED_OK = 1, 2
 # ev2h_loss_accumulate), and for the augmented training item (ev2h_event_window_build_s_ranges_aug), and for the fine-tuning item
 # (ev2h_event_window_build_ranges_flip, ev2h_finetune_resolve, ev2h_finetune_targets), and for the gradient exports (ev2h_mano_backward,
 # ev2h_segmentation_score_backward, ev2h_loss_terms_backward, ev2h_collision_penalty_backward), and for the test hooks (ev2h_dbg_*),
-# and for the fitting exports (ev2h_mano_joints_jacobian, ev2h_mano_fit, ev2h_mano_fit_opts_size), and for the event simulator
+# and for the fitting exports (ev2h_mano_joints_jacobian, ev2h_mano_fit, ev2h_mano_fit_opts_size, ev2h_mano_fit_seq,
+# ev2h_mano_fit_seq_opts_size, ev2h_mano_fit_seq_workspace_bytes), and for the event simulator
 # (ev2h_esim_scratch_bytes, ev2h_esim_step, ev2h_esim_compose), and for the pose track (ev2h_pose_track_prepare, ev2h_pose_track_rows,
 # ev2h_pose_track_hand_size).
 ABI_VERSION = 8     # 8: EV2H_PREC_F16 (one fp16 plane with f16x2's range machinery); 3: F16X2 range records; 4: ev2h_fp_mlp, ev2h_weights.fp1m; 5: window strides of the outputs; 6: ev2h_pack_weights, ev2h_weights.flags; 7: ev2h_sa_desc.xyz_out
@@ -117,6 +118,11 @@ class ManoConsts(C.Structure):
 class ManoFitOpts(C.Structure):
     _fields_ = [("lam_pose", C.c_double), ("lam_shape", C.c_double), ("mu0", C.c_double), ("ftol", C.c_double),
                 ("max_iters", C.c_int32), ("free_mask", C.c_int32)]
+
+
+class ManoFitSeqOpts(C.Structure):
+    _fields_ = [("lam_pose", C.c_double), ("lam_shape", C.c_double), ("smooth", C.c_double * 4), ("mu0", C.c_double), ("ftol", C.c_double),
+                ("max_iters", C.c_int32), ("free_mask", C.c_int32), ("share_betas", C.c_int32)]
 
 
 class PoseTrackHand(C.Structure):
@@ -155,10 +161,12 @@ EXPORTS = [
     "ev2h_event_window_build_ranges_flip", "ev2h_finetune_resolve", "ev2h_finetune_targets",
     "ev2h_mano_backward", "ev2h_segmentation_score_backward", "ev2h_loss_terms_backward", "ev2h_collision_penalty_backward",
     "ev2h_mano_joints_jacobian", "ev2h_mano_fit", "ev2h_mano_fit_opts_size",
+    "ev2h_mano_fit_seq", "ev2h_mano_fit_seq_opts_size", "ev2h_mano_fit_seq_workspace_bytes",
     "ev2h_esim_scratch_bytes", "ev2h_esim_step", "ev2h_esim_compose",
     "ev2h_pose_track_prepare", "ev2h_pose_track_rows", "ev2h_pose_track_hand_size",
     # test hooks, not part of the stable interface (include/ev2hands_hip.h: "Test hooks"; ev2hands_amd/ops.py: *_rows16, dense_zsum, ...)
     "ev2h_dbg_fp_mlp_rows16", "ev2h_dbg_gemm_zsum_supported", "ev2h_dbg_gemm_zsum", "ev2h_dbg_attn_simfold_partials", "ev2h_dbg_attn_context_rows16",
+    "ev2h_dbg_mano_fit_seq_sweeps",
 ]
 
 _lib = None
@@ -265,6 +273,13 @@ def lib() -> C.CDLL:
     L.ev2h_mano_fit.argtypes = [C.POINTER(ManoConsts), vp, ci, ci, vp, C.c_size_t, vp, C.c_size_t, C.POINTER(ManoFitOpts), vp, C.c_size_t, vp, vp, vp]
     L.ev2h_mano_fit_opts_size.restype = C.c_size_t
     L.ev2h_mano_fit_opts_size.argtypes = []
+    L.ev2h_mano_fit_seq.argtypes = [C.POINTER(ManoConsts), vp, ci, vp, ci, vp, C.c_size_t, vp, C.c_size_t, C.POINTER(ManoFitSeqOpts), vp, C.c_size_t,
+                                    vp, vp, vp, vp, vp]
+    L.ev2h_dbg_mano_fit_seq_sweeps.argtypes = L.ev2h_mano_fit_seq.argtypes + [ci]
+    L.ev2h_mano_fit_seq_opts_size.restype = C.c_size_t
+    L.ev2h_mano_fit_seq_opts_size.argtypes = []
+    L.ev2h_mano_fit_seq_workspace_bytes.restype = C.c_size_t
+    L.ev2h_mano_fit_seq_workspace_bytes.argtypes = [ci, ci, ci, ci]
     L.ev2h_esim_scratch_bytes.restype = C.c_size_t
     L.ev2h_esim_scratch_bytes.argtypes = [ci, ci, ci, ci, ci]
     L.ev2h_esim_step.argtypes = [vp, ci, ci, ci, vp, ci, vp, vp, C.c_double, C.c_double, C.c_double, C.c_double, ci, ci, ci, vp, vp, vp, vp,
@@ -315,6 +330,8 @@ def lib() -> C.CDLL:
         raise Ev2hError(f"struct layout mismatch between ev2hands_hip.h and _lib.py: {list(sizes)} vs {mine}")
     if L.ev2h_mano_fit_opts_size() != C.sizeof(ManoFitOpts):
         raise Ev2hError(f"struct layout mismatch between ev2hands_hip.h and _lib.py: ev2h_mano_fit_opts {L.ev2h_mano_fit_opts_size()} vs {C.sizeof(ManoFitOpts)}")
+    if L.ev2h_mano_fit_seq_opts_size() != C.sizeof(ManoFitSeqOpts):
+        raise Ev2hError(f"struct layout mismatch between ev2hands_hip.h and _lib.py: ev2h_mano_fit_seq_opts {L.ev2h_mano_fit_seq_opts_size()} vs {C.sizeof(ManoFitSeqOpts)}")
     if L.ev2h_pose_track_hand_size() != C.sizeof(PoseTrackHand):
         raise Ev2hError(f"struct layout mismatch between ev2hands_hip.h and _lib.py: ev2h_pose_track_hand {L.ev2h_pose_track_hand_size()} vs {C.sizeof(PoseTrackHand)}")
     if L.ev2h_abi_version() != ABI_VERSION:

@@ -462,6 +462,513 @@ __global__ __launch_bounds__(MF_THREADS) void mano_fit_kernel(FitP p) {
     }
 }
 
+// ------------------------------------------------------------------------------------------------ the fit of whole sequences
+// One least-squares problem per sequence (include/ev2hands_hip.h states it at ev2h_mano_fit_seq).  Four kernels per solve, issued
+// max_iters times by a host that reads nothing: linearise (a wavefront per frame), sweep (a wavefront per sequence: the block
+// Cholesky down the frames, the border's Schur complement, the backward pass), trial cost (per frame), decide (per sequence).
+// Every kernel reads its sequence's state word first and a finished sequence's workgroups leave before their first barrier.
+constexpr int SEQ_LINEARISE = 0, SEQ_REUSE = 1, SEQ_DONE = 2;
+
+struct SeqState {
+    double cost0, cost, mu, gmax;
+    int32_t iters, status, word, ok;      // word: SEQ_*; ok: the last sweep factored and wrote trial rows
+};
+
+struct SeqWs {                            // the workspace, carved by seq_carve
+    double *A, *g, *B, *Sf, *gsf;         // per frame: packed lower A_f [nt], g_f [n]; shared: B_f [n][10], packed S_f [55], gs_f [10]
+    double *L, *V;                        // per frame: packed L_ff [nt]; the forward pass' columns [n][ncol] (y, then the border's W)
+    double *trial, *tcost, *ttemp;        // trial rows [P]; a frame's data-plus-prior cost and its temporal rows' squares at the trial rows
+    SeqState* st;
+    int32_t *offsets, *bad;
+};
+
+struct SeqP {
+    ev2h_mano_consts c;
+    const float* params0; int ldp;
+    const float* targets; size_t t_stride;
+    const float* weights; size_t w_stride;
+    ev2h_mano_fit_seq_opts o;
+    SeqWs w;
+    int S, n;                             // n: unknowns per frame (6 + ncomps shared, else P)
+    double* out; double* frame_cost; double* stats; int32_t* info;
+};
+
+size_t seq_carve(int K, size_t F, size_t S, int shared, char* base, SeqWs* w) {
+    const size_t P = 16 + K, n = shared ? 6 + K : P, nt = n * (n + 1) / 2, ncol = shared ? 11 : 1;
+    size_t at = 0;
+    auto take = [&](size_t bytes) { char* p = base + at; at += (bytes + 7) / 8 * 8; return p; };
+    SeqWs t{};
+    t.A = (double*)take(F * nt * 8); t.g = (double*)take(F * n * 8);
+    t.B = (double*)take(shared ? F * n * NB * 8 : 0); t.Sf = (double*)take(shared ? F * 55 * 8 : 0); t.gsf = (double*)take(shared ? F * NB * 8 : 0);
+    t.L = (double*)take(F * nt * 8); t.V = (double*)take(F * n * ncol * 8);
+    t.trial = (double*)take(F * P * 8); t.tcost = (double*)take(F * 8); t.ttemp = (double*)take(F * 8);
+    t.st = (SeqState*)take(S * sizeof(SeqState));
+    t.offsets = (int32_t*)take((S + 1) * 4); t.bad = (int32_t*)take(F * 4);
+    if (w) *w = t;
+    return at;
+}
+
+__device__ __forceinline__ int seq_group(int p, int nc) { return p < 3 ? 0 : p < 3 + nc ? 1 : p < 13 + nc ? 2 : 3; }
+
+__device__ __forceinline__ int seq_of_frame(const int32_t* off, int S, int f) {
+    int lo = 0, hi = S;
+    while (hi - lo > 1) {
+        const int mid = (lo + hi) >> 1;
+        if (off[mid] <= f) lo = mid; else hi = mid;
+    }
+    return lo;
+}
+
+__device__ __forceinline__ double seq_smooth(const ev2h_mano_fit_seq_opts& o, int grp) {
+    return grp == 0 ? o.smooth[0] : grp == 1 ? o.smooth[1] : grp == 2 ? o.smooth[2] : o.smooth[3];
+}
+
+// The weights and targets of frame f, as mano_fit_kernel reads them; returns whether a target of positive weight is not finite.
+__device__ __forceinline__ int seq_load_targets(const SeqP& p, size_t f, int lane, double* s_sw, double* s_tgt) {
+    int bad = 0;
+    if (lane < 21) {
+        const float w = p.weights ? p.weights[f * p.w_stride + lane] : 1.f;
+        const bool on = w > 0.f;
+        s_sw[lane] = on ? sqrt((double)w) : 0.0;
+#pragma unroll
+        for (int cc = 0; cc < 3; ++cc) {
+            const float t = p.targets[f * p.t_stride + lane * 3 + cc];
+            s_tgt[lane * 3 + cc] = on ? (double)t : 0.0;
+            bad |= on && !isfinite(t);
+        }
+    }
+    return bad;
+}
+
+// A frame's data-plus-prior cost and the squares of its temporal rows (towards frame f - 1), at the start rows (INIT: params0 is
+// widened, a shared betas taken from the sequence's first row, and written to `out`) or at the sweep's trial rows.
+template <bool INIT>
+__global__ __launch_bounds__(MF_THREADS) void mano_seq_cost_kernel(SeqP p) {
+    __shared__ Hand h;
+    __shared__ double s_res[63 + 45 + NB], s_sw[21], s_tgt[63], s_tmp[MAXP];
+    const int f = blockIdx.x, lane = threadIdx.x, nc = p.c.ncomps, P = 16 + nc, NR = 63 + nc + NB;
+    const int s = seq_of_frame(p.w.offsets, p.S, f), first = p.w.offsets[s];
+    if (!INIT) {
+        const SeqState& st = p.w.st[s];
+        if (st.word == SEQ_DONE || !st.ok) return;
+    }
+    const int grp = seq_group(lane, nc);
+    const double lam = grp == 1 ? p.o.lam_pose : grp == 2 ? p.o.lam_shape : 0.0;
+    const bool from_first = p.o.share_betas && grp == 2;
+    hand_load_constants(p.c, h, lane);
+    int bad = 0;
+    double tsq = 0.0;
+    if (lane < P) {
+        double v, prev = 0.0;
+        if (INIT) {
+            v = (double)p.params0[(size_t)(from_first ? first : f) * p.ldp + lane];
+            if (f > first) prev = (double)p.params0[(size_t)(from_first ? first : f - 1) * p.ldp + lane];
+            p.out[(size_t)f * P + lane] = v;
+            bad |= !isfinite(v);
+        } else {
+            v = p.w.trial[(size_t)f * P + lane];
+            if (f > first) prev = p.w.trial[(size_t)(f - 1) * P + lane];
+        }
+        h.theta[lane] = v;
+        const double sm = seq_smooth(p.o, grp);
+        if (f > first && sm > 0.0) { const double d = v - prev; tsq = sm * (d * d); }
+    }
+    if (lane < MAXP) s_tmp[lane] = lane < P ? tsq : 0.0;
+    bad |= seq_load_targets(p, (size_t)f, lane, s_sw, s_tgt);
+    if (INIT) {
+        bad = __syncthreads_or(bad);
+        if (lane == 0) p.w.bad[f] = bad;
+        if (bad) {                                                // (the sequence ends with status 2: its frames' costs are not read)
+            if (lane == 0) { p.w.tcost[f] = 0.0; p.w.ttemp[f] = 0.0; }
+            return;
+        }
+    }
+    hand_forward(p.c, h, lane);
+    if (lane < 63) {
+        const double sw = s_sw[lane / 3];
+        s_res[lane] = sw > 0.0 ? sw * (1000.0 * (h.joints[lane] - s_tgt[lane])) : 0.0;
+    }
+    if (lane < P && (grp == 1 || grp == 2)) s_res[63 + lane - 3] = sqrt(lam) * h.theta[lane];
+    __syncthreads();
+    if (lane == 0) {
+        double acc = 0.0;
+        for (int r = 0; r < NR; ++r) acc = fma(s_res[r], s_res[r], acc);
+        double t = 0.0;
+        for (int i = 0; i < P; ++i) t += s_tmp[i];
+        p.w.tcost[f] = acc;
+        p.w.ttemp[f] = t;
+    }
+}
+
+// A_f, g_f (and B_f, S_f, gs_f with a shared betas) at the accepted rows.  The data and prior parts are mano_fit_kernel's; g also
+// carries the temporal rows' gradient, whose Hessian terms the sweep adds.  A frozen parameter's row, column, diagonal and g are 0
+// here (the sweep sets its diagonal).
+__global__ __launch_bounds__(MF_THREADS) void mano_seq_linearise_kernel(SeqP p) {
+    __shared__ Hand h;
+    __shared__ double s_big[63 * MAXP];
+    __shared__ double s_theta[MAXP], s_res[63], s_sw[21], s_tgt[63];
+    const int f = blockIdx.x, lane = threadIdx.x, nc = p.c.ncomps, P = 16 + nc, n = p.n, nt = n * (n + 1) / 2;
+    const int s = seq_of_frame(p.w.offsets, p.S, f), first = p.w.offsets[s], last = p.w.offsets[s + 1] - 1;
+    if (p.w.st[s].word != SEQ_LINEARISE) return;
+    const bool shared = p.o.share_betas != 0;
+    const int b0 = 3 + nc;                                                               // the first betas column
+    const int grp = seq_group(lane, nc);
+    const bool is_free = lane < P && ((p.o.free_mask >> grp) & 1);
+    const double lam = grp == 1 ? p.o.lam_pose : grp == 2 ? p.o.lam_shape : 0.0;
+    hand_load_constants(p.c, h, lane);
+    if (lane < P) {
+        const double v = p.out[(size_t)f * P + lane];
+        s_theta[lane] = v;
+        h.theta[lane] = v;
+    }
+    seq_load_targets(p, (size_t)f, lane, s_sw, s_tgt);
+    hand_forward(p.c, h, lane);
+    if (lane < 63) {
+        const double sw = s_sw[lane / 3];
+        s_res[lane] = sw > 0.0 ? sw * (1000.0 * (h.joints[lane] - s_tgt[lane])) : 0.0;
+    }
+    if (lane < P) {
+        hand_tangent(p.c, h, lane, s_big, P);
+        for (int r = 0; r < 63; ++r) {
+            const double sw = s_sw[r / 3];
+            s_big[r * P + lane] = (is_free && sw > 0.0) ? sw * (1000.0 * s_big[r * P + lane]) : 0.0;
+        }
+    }
+    __syncthreads();
+    {
+        int i = 0, j = lane;
+        while (j > i) { j -= i + 1; ++i; }
+        const int ntri = P * (P + 1) / 2;
+        for (int e = lane; e < ntri; e += MF_THREADS) {
+            double acc = 0.0;
+            for (int r = 0; r < 63; ++r) acc = fma(s_big[r * P + i], s_big[r * P + j], acc);
+            const int gi = seq_group(i, nc), gj = seq_group(j, nc);
+            if (i == j && ((p.o.free_mask >> gi) & 1)) acc += gi == 1 ? p.o.lam_pose : gi == 2 ? p.o.lam_shape : 0.0;
+            if (!shared) p.w.A[(size_t)f * nt + e] = acc;
+            else {
+                const int li = i < b0 ? i : i - NB, lj = j < b0 ? j : j - NB;              // per-frame indices (where i, j are no betas)
+                if (gi != 2 && gj != 2) p.w.A[(size_t)f * nt + tri(li, lj)] = acc;
+                else if (gi == 2 && gj == 2) p.w.Sf[(size_t)f * 55 + tri(i - b0, j - b0)] = acc;
+                else if (gi == 2) p.w.B[((size_t)f * n + lj) * NB + (i - b0)] = acc;     // j < b0 <= i
+                else p.w.B[((size_t)f * n + li) * NB + (j - b0)] = acc;                  // i a transl column, j a betas column
+            }
+            j += MF_THREADS;
+            while (j > i) { j -= i + 1; ++i; }
+        }
+    }
+    if (lane < P) {
+        double acc = 0.0;
+        for (int r = 0; r < 63; ++r) acc = fma(s_big[r * P + lane], s_res[r], acc);
+        acc = fma(lam, s_theta[lane], acc);
+        const double sm = seq_smooth(p.o, grp);
+        if (sm > 0.0) {
+            double t = 0.0;
+            if (f > first) t += sm * (s_theta[lane] - p.out[(size_t)(f - 1) * P + lane]);
+            if (f < last) t += sm * (s_theta[lane] - p.out[(size_t)(f + 1) * P + lane]);
+            acc += t;
+        }
+        const double gv = is_free ? acc : 0.0;
+        if (shared && grp == 2) p.w.gsf[(size_t)f * NB + lane - b0] = gv;
+        else p.w.g[(size_t)f * n + (shared && lane >= b0 ? lane - NB : lane)] = gv;
+    }
+}
+
+// In-place Cholesky of the packed lower m x m matrix in LDS, lane i owns row i (mano_fit_kernel's).  Uniform result.
+__device__ __forceinline__ bool seq_cholesky(double* M, int m, int lane) {
+    for (int j = 0; j < m; ++j) {
+        double s = 0.0;
+        if (lane >= j && lane < m) {
+            s = M[tri(lane, j)];
+            for (int k = 0; k < j; ++k) s -= M[tri(lane, k)] * M[tri(j, k)];
+        }
+        const double piv = __shfl(s, j, 64);
+        if (!(isfinite(piv) && piv > 0.0)) return false;
+        const double d = sqrt(piv);
+        if (lane == j) M[tri(j, j)] = d;
+        else if (lane > j && lane < m) M[tri(lane, j)] = s / d;
+        __syncthreads();
+    }
+    return true;
+}
+
+// L y = v, lane i keeps element i; lp = min(lane, m - 1)
+__device__ __forceinline__ double seq_forward_solve(const double* L, int m, int lane, int lp, double v) {
+    for (int j = 0; j < m; ++j) {
+        const double yj = __shfl(v / L[tri(lp, lp)], j, 64);
+        if (lane == j) v = yj;
+        else if (lane > j && lane < m) v -= L[tri(lane, j)] * yj;
+    }
+    return v;
+}
+
+// L^T d = v
+__device__ __forceinline__ double seq_backward_solve(const double* L, int m, int lane, int lp, double v) {
+    for (int j = m - 1; j >= 0; --j) {
+        const double dj = __shfl(v / L[tri(lp, lp)], j, 64);
+        if (lane == j) v = dj;
+        else if (lane < j) v -= L[tri(j, lane)] * dj;
+    }
+    return v;
+}
+
+// The solve of one sequence: (H + mu D) delta = -g with H block-tridiagonal in the frames (off-diagonal blocks -diag(smooth)) and,
+// SHARED, bordered by the betas' 10 columns.  Down the frames: L_ff L_ff^T = M_f - E_f E_f^T with E_f = L_{f,f-1} =
+// -diag(smooth) L_{f-1,f-1}^{-T}, formed from X = L_{f-1,f-1}^{-1} (lane j solves column j); the right-hand side and the border's
+// columns C_f = [-g_f | B_f] go through the same pass, V_f = L_ff^{-1} (C_f + diag(smooth) X^T V_{f-1}).  Then the Schur complement
+// S + mu D_s - sum_f W_f^T W_f, its Cholesky and the border's step, and up the frames
+// delta_f = L_ff^{-T} (y_f - W_f delta_s + L_ff^{-1} (smooth * delta_{f+1})).  Kept per frame: the packed L_ff and V_f.
+template <bool SHARED>
+__global__ __launch_bounds__(MF_THREADS) void mano_seq_sweep_kernel(SeqP p) {
+    constexpr int NCOL = SHARED ? 1 + NB : 1;
+    __shared__ double s_L[NTRI], s_X[NTRI], s_V[MAXP * NCOL], s_sm[MAXP], s_S[55], s_ds[NB];
+    const int s = blockIdx.x, lane = threadIdx.x, nc = p.c.ncomps, P = 16 + nc, n = p.n, nt = n * (n + 1) / 2;
+    SeqState* st = p.w.st + s;
+    if (st->word == SEQ_DONE) return;
+    const int first = p.w.offsets[s], F = p.w.offsets[s + 1] - first;
+    const double mu = st->mu;
+    const int pp = (SHARED && lane >= 3 + nc) ? lane + NB : lane;                        // this lane's column of a parameter row
+    const int grp = seq_group(pp, nc);
+    const bool is_free = lane < n && ((p.o.free_mask >> grp) & 1);
+    const double sm = is_free ? seq_smooth(p.o, grp) : 0.0;
+    const int lp = min(lane, n - 1);
+    if (lane < MAXP) s_sm[lane] = sm;
+
+    // max |g| of the linearisation, and the border's gradient, frame by frame
+    double gmax = 0.0, gs = 0.0;
+    for (size_t e = lane; e < (size_t)F * n; e += MF_THREADS) {
+        double m = fabs(p.w.g[(size_t)first * n + e]);
+        if (m != m) m = INFINITY;
+        gmax = fmax(gmax, m);
+    }
+    if (SHARED && lane < NB) {
+        for (int k = 0; k < F; ++k) gs += p.w.gsf[(size_t)(first + k) * NB + lane];
+        double m = fabs(gs);
+        if (m != m) m = INFINITY;
+        gmax = fmax(gmax, m);
+    }
+#pragma unroll
+    for (int o = 32; o >= 1; o >>= 1) gmax = fmax(gmax, __shfl_xor(gmax, o, 64));
+
+    int ea = 0, eb = lane;                                                               // SHARED: lane e < 55 owns entry (ea, eb) of the 10 x 10 blocks
+    while (eb > ea) { eb -= ea + 1; ++ea; }
+    double accS = 0.0, accW = 0.0, accWy = 0.0;
+    bool ok = true;
+    __syncthreads();
+    for (int k = 0; k < F; ++k) {
+        const size_t f = (size_t)first + k;
+        double v[NCOL];                                                                  // the frame's columns [-g_f | B_f] and its S_f entry: asked for first, used last
+#pragma unroll
+        for (int c = 0; c < NCOL; ++c) v[c] = 0.0;
+        if (lane < n) {
+            v[0] = -p.w.g[f * n + lane];
+            if (SHARED) {
+#pragma unroll
+                for (int c = 0; c < NB; ++c) v[1 + c] = p.w.B[(f * n + lane) * NB + c];
+            }
+        }
+        const double sf = (SHARED && lane < 55) ? p.w.Sf[f * 55 + lane] : 0.0;
+        if (k > 0) {                                                                     // X = L_{k-1}^{-1}, s_L still holds L_{k-1}
+            if (lane < n) {
+                for (int i = lane; i < n; ++i) {
+                    double acc = i == lane ? 1.0 : 0.0;
+                    for (int kk = lane; kk < i; ++kk) acc -= s_L[tri(i, kk)] * s_X[tri(kk, lane)];
+                    s_X[tri(i, lane)] = acc / s_L[tri(i, i)];
+                }
+            }
+            __syncthreads();
+        }
+        for (int e = lane; e < nt; e += MF_THREADS) s_L[e] = p.w.A[f * nt + e];
+        __syncthreads();
+        if (lane < n) {
+            double hd = 1.0;
+            if (is_free) {
+                hd = s_L[tri(lane, lane)];
+                if (k > 0) hd += sm;
+                if (k < F - 1) hd += sm;
+            }
+            s_L[tri(lane, lane)] = hd + mu * (hd > 0.0 ? hd : 1.0);
+            if (k > 0 && sm != 0.0) {
+                for (int j = 0; j <= lane; ++j) {
+                    const double sj = s_sm[j];
+                    if (sj == 0.0) continue;
+                    double acc = 0.0;
+                    for (int kk = lane; kk < n; ++kk) acc = fma(s_X[tri(kk, lane)], s_X[tri(kk, j)], acc);
+                    s_L[tri(lane, j)] -= (sm * sj) * acc;
+                }
+            }
+        }
+        __syncthreads();
+        ok = seq_cholesky(s_L, n, lane);
+        if (!ok) break;
+        for (int e = lane; e < nt; e += MF_THREADS) p.w.L[f * nt + e] = s_L[e];
+        if (lane < n) {
+            if (k > 0 && sm != 0.0) {
+#pragma unroll
+                for (int c = 0; c < NCOL; ++c) {
+                    double acc = 0.0;
+                    for (int kk = lane; kk < n; ++kk) acc = fma(s_X[tri(kk, lane)], s_V[kk * NCOL + c], acc);
+                    v[c] = fma(sm, acc, v[c]);
+                }
+            }
+        }
+        __syncthreads();
+        {                                                                                // L_ff V = C, the columns abreast (seq_forward_solve's arithmetic per column)
+            const double dl = s_L[tri(lp, lp)];
+            for (int j = 0; j < n; ++j) {
+                const double l = (lane > j && lane < n) ? s_L[tri(lane, j)] : 0.0;
+#pragma unroll
+                for (int c = 0; c < NCOL; ++c) {
+                    const double yj = __shfl(v[c] / dl, j, 64);
+                    if (lane == j) v[c] = yj;
+                    else if (lane > j && lane < n) v[c] -= l * yj;
+                }
+            }
+        }
+        if (lane < n) {
+#pragma unroll
+            for (int c = 0; c < NCOL; ++c) { s_V[lane * NCOL + c] = v[c]; p.w.V[(f * n + lane) * NCOL + c] = v[c]; }
+        }
+        __syncthreads();
+        if (SHARED) {
+            if (lane < 55) {
+                accS += sf;
+                double w = 0.0;
+                for (int i = 0; i < n; ++i) w = fma(s_V[i * NCOL + 1 + ea], s_V[i * NCOL + 1 + eb], w);
+                accW += w;
+            }
+            if (lane < NB) {
+                double w = 0.0;
+                for (int i = 0; i < n; ++i) w = fma(s_V[i * NCOL + 1 + lane], s_V[i * NCOL], w);
+                accWy += w;
+            }
+        }
+    }
+    if (SHARED && ok) {
+        const bool free_b = (p.o.free_mask >> 2) & 1;
+        if (lane < 55) {
+            double val = accS;
+            if (ea == eb) {
+                const double hd = free_b ? accS : 1.0;
+                val = hd + mu * (hd > 0.0 ? hd : 1.0);
+            }
+            s_S[lane] = val - accW;
+        }
+        __syncthreads();
+        ok = seq_cholesky(s_S, NB, lane);
+        if (ok) {
+            const int lb = min(lane, NB - 1);
+            double v = lane < NB ? -gs - accWy : 0.0;
+            v = seq_forward_solve(s_S, NB, lane, lb, v);
+            v = seq_backward_solve(s_S, NB, lane, lb, v);
+            if (lane < NB) s_ds[lane] = v;
+            __syncthreads();
+            const double* row0 = p.out + (size_t)first * P + 3 + nc;                     // the shared betas: every row holds it
+            for (size_t e = lane; e < (size_t)F * NB; e += MF_THREADS) {
+                const int b = (int)(e % NB);
+                p.w.trial[((size_t)first + e / NB) * P + 3 + nc + b] = free_b ? row0[b] + s_ds[b] : row0[b];
+            }
+        }
+    }
+    if (!ok) {                                                                           // (uniform: every lane saw the same pivot)
+        if (lane == 0) { st->ok = 0; st->gmax = gmax; }
+        return;
+    }
+    double dnext = 0.0;
+    for (int k = F - 1; k >= 0; --k) {
+        const size_t f = (size_t)first + k;
+        __syncthreads();
+        for (int e = lane; e < nt; e += MF_THREADS) s_L[e] = p.w.L[f * nt + e];
+        __syncthreads();
+        double z = 0.0;
+        if (lane < n) {
+            z = p.w.V[(f * n + lane) * NCOL];
+            if (SHARED) {
+#pragma unroll
+                for (int c = 0; c < NB; ++c) z -= p.w.V[(f * n + lane) * NCOL + 1 + c] * s_ds[c];
+            }
+        }
+        if (k < F - 1) z += seq_forward_solve(s_L, n, lane, lp, sm * dnext);
+        const double d = seq_backward_solve(s_L, n, lane, lp, z);
+        if (lane < n) {
+            const double cur = p.out[f * P + pp];
+            p.w.trial[f * P + pp] = is_free ? cur + d : cur;
+        }
+        dnext = lane < n ? d : 0.0;
+    }
+    if (lane == 0) { st->ok = 1; st->gmax = gmax; }
+}
+
+// A sequence's cost at the rows the cost kernel evaluated and what follows from it.  The sum: lane l adds the frames l, l + 64, ...
+// in order, first their data-plus-prior costs, then their temporal squares; the 64 partial sums meet in a butterfly -- an order that
+// depends on F_s alone.  INIT: the start rows' cost, status 2 for a sequence with a bad frame.  Otherwise accept / reject.
+template <bool INIT>
+__global__ __launch_bounds__(MF_THREADS) void mano_seq_decide_kernel(SeqP p) {
+    const int s = blockIdx.x, lane = threadIdx.x, P = 16 + p.c.ncomps;
+    SeqState* st = p.w.st + s;
+    SeqState cur{};
+    if (!INIT) {
+        cur = *st;
+        if (cur.word == SEQ_DONE) return;
+        __syncthreads();                                                                 // (lane 0 rewrites *st below)
+    }
+    const int first = p.w.offsets[s], F = p.w.offsets[s + 1] - first;
+    if (INIT) {
+        int bad = 0;
+        for (int k = lane; k < F; k += MF_THREADS) bad |= p.w.bad[first + k];
+        bad = __syncthreads_or(bad);
+        if (bad) {
+            const double nan = __longlong_as_double(0x7ff8000000000000ll);
+            for (size_t e = lane; e < (size_t)F * P; e += MF_THREADS)
+                p.out[(size_t)first * P + e] = (double)p.params0[((size_t)first + e / P) * p.ldp + e % P];
+            for (int k = lane; k < F; k += MF_THREADS) p.frame_cost[first + k] = nan;
+            if (lane == 0) {
+                cur.cost0 = nan; cur.cost = nan; cur.mu = p.o.mu0; cur.gmax = nan; cur.iters = 0; cur.status = 2; cur.word = SEQ_DONE; cur.ok = 0;
+                *st = cur;
+                p.stats[s * 4] = nan; p.stats[s * 4 + 1] = nan; p.stats[s * 4 + 2] = p.o.mu0; p.stats[s * 4 + 3] = nan;
+                p.info[s * 2] = 0; p.info[s * 2 + 1] = 2;
+            }
+            return;
+        }
+    }
+    double total = 0.0;
+    if (INIT || cur.ok) {
+        double data = 0.0, temp = 0.0;
+        for (int k = lane; k < F; k += MF_THREADS) data += p.w.tcost[first + k];
+        for (int k = lane; k < F; k += MF_THREADS) temp += p.w.ttemp[first + k];
+#pragma unroll
+        for (int o = 32; o >= 1; o >>= 1) { data += __shfl_xor(data, o, 64); temp += __shfl_xor(temp, o, 64); }
+        total = data + temp;
+    }
+    bool accept;
+    if (INIT) {
+        cur.cost0 = total; cur.cost = total; cur.mu = p.o.mu0; cur.gmax = 0.0; cur.iters = 0; cur.ok = 0;
+        cur.status = total == 0.0 ? 0 : 1;
+        cur.word = cur.status == 0 ? SEQ_DONE : SEQ_LINEARISE;
+        accept = true;                                                                   // (the frames' costs are taken over, the rows are in place)
+    } else {
+        ++cur.iters;
+        accept = cur.ok && isfinite(total) && total < cur.cost;
+        if (accept) {
+            if (cur.cost - total <= p.o.ftol * cur.cost || total == 0.0) cur.status = 0;
+            cur.cost = total;
+            cur.mu = fmax(cur.mu / 10.0, 1e-12);
+            cur.word = SEQ_LINEARISE;
+            for (size_t e = lane; e < (size_t)F * P; e += MF_THREADS) p.out[(size_t)first * P + e] = p.w.trial[(size_t)first * P + e];
+        } else {
+            cur.mu = fmin(cur.mu * 10.0, 1e12);
+            cur.word = SEQ_REUSE;
+        }
+        if (cur.status != 1 || cur.iters >= p.o.max_iters) cur.word = SEQ_DONE;
+    }
+    if (accept)
+        for (int k = lane; k < F; k += MF_THREADS) p.frame_cost[first + k] = p.w.tcost[first + k];
+    if (lane == 0) {
+        *st = cur;
+        p.stats[s * 4] = cur.cost0; p.stats[s * 4 + 1] = cur.cost; p.stats[s * 4 + 2] = cur.mu; p.stats[s * 4 + 3] = cur.gmax;
+        p.info[s * 2] = cur.iters; p.info[s * 2 + 1] = cur.status;
+    }
+}
+
 int check_consts(const ev2h_mano_consts* c) {
     EV2H_CHECK_ARG(c->hands_mean && c->comps && c->blend_T && c->v_template && c->J_template && c->J_shape && c->weights);
     EV2H_CHECK_ARG(c->ncomps >= 1 && c->ncomps <= 45);
@@ -507,4 +1014,79 @@ extern "C" int ev2h_mano_fit(const ev2h_mano_consts* c, const float* params0, in
     mano_fit_kernel<<<B, MF_THREADS, 0, (hipStream_t)stream>>>(p);
     EV2H_CHECK_LAUNCH();
     return EV2H_OK;
+}
+
+extern "C" size_t ev2h_mano_fit_seq_opts_size(void) { return sizeof(ev2h_mano_fit_seq_opts); }
+
+extern "C" size_t ev2h_mano_fit_seq_workspace_bytes(int K, int n_frames, int S, int share_betas) {
+    if (K < 1 || K > 45 || S < 1 || n_frames < S || (share_betas != 0 && share_betas != 1)) return 0;
+    return seq_carve(K, (size_t)n_frames, (size_t)S, share_betas, nullptr, nullptr);
+}
+
+// n_sweeps < 0: the fit.  n_sweeps >= 0 (ev2h_dbg_mano_fit_seq_sweeps): the start rows' cost, one linearisation, n_sweeps sweeps.
+static int seq_run(const ev2h_mano_consts* c, const float* params0, int ldp, const int32_t* offsets, int S, const float* targets,
+                   size_t targets_stride, const float* weights, size_t weights_stride, const ev2h_mano_fit_seq_opts* opts, void* workspace,
+                   size_t workspace_bytes, double* out_rows, double* per_frame_cost, double* stats, int32_t* info, ev2h_stream_t stream,
+                   int n_sweeps) {
+    EV2H_CHECK_ARG(c && params0 && offsets && targets && opts && workspace && out_rows && per_frame_cost && stats && info && S >= 1);
+    if (int rc = check_consts(c)) return rc;
+    const int P = 16 + c->ncomps;
+    EV2H_CHECK_ARG(ldp >= P);
+    EV2H_CHECK_ARG((targets_stride == 0 || targets_stride >= 63) && (weights_stride == 0 || weights_stride >= 21));
+    EV2H_CHECK_ARG(opts->max_iters >= 1 && opts->max_iters <= 64);
+    EV2H_CHECK_ARG(std::isfinite(opts->lam_pose) && opts->lam_pose >= 0.0 && std::isfinite(opts->lam_shape) && opts->lam_shape >= 0.0);
+    EV2H_CHECK_ARG(std::isfinite(opts->mu0) && opts->mu0 >= 0.0 && std::isfinite(opts->ftol) && opts->ftol >= 0.0);
+    for (int g = 0; g < 4; ++g) EV2H_CHECK_ARG(std::isfinite(opts->smooth[g]) && opts->smooth[g] >= 0.0);
+    EV2H_CHECK_ARG(opts->share_betas == 0 || opts->share_betas == 1);
+    EV2H_CHECK_ARG(!opts->share_betas || opts->smooth[2] == 0.0);
+    EV2H_CHECK_ARG(offsets[0] == 0);
+    for (int s = 0; s < S; ++s) EV2H_CHECK_ARG(offsets[s + 1] > offsets[s]);
+    const int F = offsets[S];
+    SeqP p{};
+    EV2H_CHECK_ARG(((uintptr_t)workspace & 7) == 0 && workspace_bytes >= seq_carve(c->ncomps, (size_t)F, (size_t)S, opts->share_betas, (char*)workspace, &p.w));
+    p.c = *c; p.params0 = params0; p.ldp = ldp;
+    p.targets = targets; p.t_stride = targets_stride ? targets_stride : (size_t)63;
+    p.weights = weights; p.w_stride = weights_stride ? weights_stride : (size_t)21;
+    p.o = *opts;
+    p.S = S; p.n = opts->share_betas ? 6 + c->ncomps : P;
+    p.out = out_rows; p.frame_cost = per_frame_cost; p.stats = stats; p.info = info;
+    hipStream_t st = (hipStream_t)stream;
+    EV2H_CHECK_HIP(hipMemcpyAsync(p.w.offsets, offsets, (size_t)(S + 1) * sizeof(int32_t), hipMemcpyHostToDevice, st));
+    mano_seq_cost_kernel<true><<<F, MF_THREADS, 0, st>>>(p);
+    mano_seq_decide_kernel<true><<<S, MF_THREADS, 0, st>>>(p);
+    auto sweep = [&]() {
+        if (opts->share_betas) mano_seq_sweep_kernel<true><<<S, MF_THREADS, 0, st>>>(p);
+        else mano_seq_sweep_kernel<false><<<S, MF_THREADS, 0, st>>>(p);
+    };
+    if (n_sweeps >= 0) {
+        mano_seq_linearise_kernel<<<F, MF_THREADS, 0, st>>>(p);
+        for (int it = 0; it < n_sweeps; ++it) sweep();
+        EV2H_CHECK_LAUNCH();
+        return EV2H_OK;
+    }
+    for (int it = 0; it < opts->max_iters; ++it) {
+        mano_seq_linearise_kernel<<<F, MF_THREADS, 0, st>>>(p);
+        sweep();
+        mano_seq_cost_kernel<false><<<F, MF_THREADS, 0, st>>>(p);
+        mano_seq_decide_kernel<false><<<S, MF_THREADS, 0, st>>>(p);
+    }
+    EV2H_CHECK_LAUNCH();
+    return EV2H_OK;
+}
+
+extern "C" int ev2h_mano_fit_seq(const ev2h_mano_consts* c, const float* params0, int ldp, const int32_t* offsets, int S, const float* targets,
+                                 size_t targets_stride, const float* weights, size_t weights_stride, const ev2h_mano_fit_seq_opts* opts,
+                                 void* workspace, size_t workspace_bytes, double* out_rows, double* per_frame_cost, double* stats, int32_t* info,
+                                 ev2h_stream_t stream) {
+    return seq_run(c, params0, ldp, offsets, S, targets, targets_stride, weights, weights_stride, opts, workspace, workspace_bytes, out_rows,
+                   per_frame_cost, stats, info, stream, -1);
+}
+
+extern "C" int ev2h_dbg_mano_fit_seq_sweeps(const ev2h_mano_consts* c, const float* params0, int ldp, const int32_t* offsets, int S,
+                                            const float* targets, size_t targets_stride, const float* weights, size_t weights_stride,
+                                            const ev2h_mano_fit_seq_opts* opts, void* workspace, size_t workspace_bytes, double* out_rows,
+                                            double* per_frame_cost, double* stats, int32_t* info, ev2h_stream_t stream, int n_sweeps) {
+    EV2H_CHECK_ARG(n_sweeps >= 0 && n_sweeps <= 64);
+    return seq_run(c, params0, ldp, offsets, S, targets, targets_stride, weights, weights_stride, opts, workspace, workspace_bytes, out_rows,
+                   per_frame_cost, stats, info, stream, n_sweeps);
 }

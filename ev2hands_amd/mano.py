@@ -232,6 +232,84 @@ class ManoHand:
                                             C.byref(opts), out.data_ptr(), 0, stats.data_ptr(), info.data_ptr(), _lib.stream_handle()), "ev2h_mano_fit")
         return ManoFit(self, out, stats, info)
 
+    def fit_sequence(self, j3d, offsets=None, weights=None, init="frames", smooth=(0.0, 0.0, 0.0, 0.0), share_betas: bool = True,
+                     lam_pose: float = 0.0, lam_shape: float = 0.0, free=_lib.FIT_GROUPS, max_iters: int = 32, mu0: float = 1e-3,
+                     ftol: float = 1e-12, _sweeps_only=None):
+        """ev2h_mano_fit_seq: fit whole sequences of one hand, one least-squares problem per sequence with first-difference
+        smoothness between neighbouring frames and (share_betas) one betas vector (include/ev2hands_hip.h states the problem and the
+        Levenberg-Marquardt rules).  j3d float32 [F, 21, 3] in metres and weights [F, 21] as `fit` takes them; a frame without any
+        positive weight is carried by its neighbours.  offsets: host integers [S + 1] starting at 0 and increasing (a list, an array
+        or a CPU tensor; a device tensor would have to be read back), None = one sequence.  smooth: four weights over FIT_GROUPS or a
+        dict over some of their names (with share_betas the betas' must be 0).  init: float32 [F, 16 + ncomps] start rows, or
+        "frames": `fit(init="rigid")` of every frame with the same priors and `free`, a frame without data taking the row of the
+        nearest earlier frame of its sequence that has data (the nearest later one in a leading gap), and with share_betas every
+        row's betas set to the mean over the sequence's frames that have data (`sequence_start_rows`).  -> ManoSequenceFit.
+        No host synchronisation.  (_sweeps_only = n: the test hook ev2h_dbg_mano_fit_seq_sweeps instead, for tools/mano_fit_seq_timing.py.)"""
+        P, K = 16 + self.ncomps, self.ncomps
+        if not isinstance(j3d, torch.Tensor) or j3d.dim() != 3 or j3d.shape[0] < 1:
+            raise ValueError("j3d must be a float32 [F, 21, 3] CUDA tensor with F >= 1")
+        F = int(j3d.shape[0])
+        _lib._dev_tensor(j3d, "j3d", torch.float32, (F, 21, 3), self.device, contiguous=False)
+        if j3d.stride()[1:] != (3, 1) or (F > 1 and j3d.stride(0) < 63):
+            raise ValueError(f"j3d: windows must be dense and must not overlap, got strides {j3d.stride()}")
+        if weights is not None:
+            if not isinstance(weights, torch.Tensor) or tuple(weights.shape) != (F, 21) or weights.device != self.device or \
+                    not (weights.dtype.is_floating_point or weights.dtype == torch.bool):
+                raise ValueError(f"weights must be a floating-point or bool tensor [{F}, 21] on {self.device}")
+            if weights.dtype != torch.float32 or weights.stride(1) != 1 or (F > 1 and weights.stride(0) < 21):
+                weights = weights.to(torch.float32).contiguous()
+        unknown = [g for g in free if g not in _lib.FIT_GROUPS]
+        if unknown or isinstance(free, str):
+            raise ValueError(f"free holds names of {_lib.FIT_GROUPS}, got {free!r}")
+        if isinstance(smooth, dict):
+            if any(g not in _lib.FIT_GROUPS for g in smooth):
+                raise ValueError(f"smooth holds names of {_lib.FIT_GROUPS}, got {sorted(smooth)}")
+            smooth = [smooth.get(g, 0.0) for g in _lib.FIT_GROUPS]
+        smooth = [float(v) for v in smooth]
+        if len(smooth) != 4:
+            raise ValueError(f"smooth holds four weights over {_lib.FIT_GROUPS}")
+        if offsets is None:
+            offsets = [0, F]
+        if isinstance(offsets, torch.Tensor):
+            if offsets.device.type != "cpu":
+                raise ValueError("offsets are host integers: a device tensor would have to be read back")
+            offsets = offsets.tolist()
+        offsets = [int(v) for v in offsets]
+        S = len(offsets) - 1
+        if S < 1 or offsets[0] != 0 or offsets[-1] != F or any(b <= a for a, b in zip(offsets, offsets[1:])):
+            raise ValueError(f"offsets must run from 0 to {F}, increasing, got {offsets[:4]}...")
+        if isinstance(init, str):
+            if init != "frames":
+                raise ValueError('init is a float32 tensor or "frames"')
+            per_frame = self.fit(j3d, weights, init="rigid", lam_pose=lam_pose, lam_shape=lam_shape, free=free, max_iters=max_iters, mu0=mu0, ftol=ftol)
+            has = torch.ones(F, dtype=torch.bool, device=self.device) if weights is None else (weights > 0).any(1)
+            init = sequence_start_rows(per_frame.params, has, offsets, K, bool(share_betas))
+        if self._rows(init, "init")[0] != F:
+            raise ValueError(f"init must have {F} rows")
+        opts = _lib.ManoFitSeqOpts(float(lam_pose), float(lam_shape), (C.c_double * 4)(*smooth), float(mu0), float(ftol), int(max_iters),
+                                   sum(1 << i for i, g in enumerate(_lib.FIT_GROUPS) if g in free), 1 if share_betas else 0)
+        L = _lib.lib()
+        nbytes = int(L.ev2h_mano_fit_seq_workspace_bytes(K, F, S, opts.share_betas))
+        if nbytes == 0:
+            raise ValueError("ev2h_mano_fit_seq_workspace_bytes refused the sizes")
+        ws = torch.empty(nbytes // 8, device=self.device, dtype=torch.float64)
+        out = torch.empty(F, P, device=self.device, dtype=torch.float64)
+        frame_cost = torch.empty(F, device=self.device, dtype=torch.float64)
+        stats = torch.empty(S, 4, device=self.device, dtype=torch.float64)
+        info = torch.empty(S, 2, device=self.device, dtype=torch.int32)
+        off = (C.c_int32 * (S + 1))(*offsets)
+        c = self.consts()
+        args = (C.byref(c), init.data_ptr(), int(init.stride(0)) if F > 1 else P, off, S, j3d.data_ptr(), int(j3d.stride(0)) if F > 1 else 0,
+                _lib.ptr(weights), int(weights.stride(0)) if weights is not None and F > 1 else 0, C.byref(opts), ws.data_ptr(), nbytes,
+                out.data_ptr(), frame_cost.data_ptr(), stats.data_ptr(), info.data_ptr(), _lib.stream_handle())
+        if _sweeps_only is None:
+            _lib.check(L.ev2h_mano_fit_seq(*args), "ev2h_mano_fit_seq")
+        else:
+            _lib.check(L.ev2h_dbg_mano_fit_seq_sweeps(*args, int(_sweeps_only)), "ev2h_dbg_mano_fit_seq_sweeps")
+        fit = ManoSequenceFit(self, out, frame_cost, stats, info, offsets, bool(share_betas))
+        fit._offsets_host = off                                   # (the upload of the offsets is queued on the stream: its source lives as long as the result)
+        return fit
+
 
 class ManoFit:
     """What ManoHand.fit returns, all device tensors: `params64` float64 [B, 16 + ncomps] (the last accepted rows), `params` = the same
@@ -255,6 +333,45 @@ class ManoFit:
             with torch.no_grad():
                 self._output = self._hand(global_orient=self.global_orient, hand_pose=self.hand_pose, betas=self.betas, transl=self.transl)
         return self._output
+
+
+class ManoSequenceFit(ManoFit):
+    """What ManoHand.fit_sequence returns, all device tensors: ManoFit's `params64` / `params` and the four views with one row per
+    frame; `frame_cost` float64 [F], a frame's data-plus-prior cost at its row; `betas_shared` float32 [S, 10] (None without
+    sharing: the first row of each sequence, every row of a sequence holds the same); and per SEQUENCE `cost0`, `cost` (the frames'
+    costs plus the temporal rows' squares), `mu`, `gmax`, `iterations`, `status` [S] (2: a non-finite start value or target of
+    positive weight somewhere in the sequence, whose rows are the start rows).  `offsets`: the host list.  `output` as ManoFit's."""
+
+    def __init__(self, hand, params64, frame_cost, stats, info, offsets, shared):
+        super().__init__(hand, params64, stats, info)
+        self.frame_cost, self.offsets = frame_cost, list(offsets)
+        self.betas_shared = self.betas[torch.as_tensor(offsets[:-1], device=params64.device)] if shared else None
+
+
+def sequence_start_rows(rows, has_data, offsets, ncomps: int, share_betas: bool = True):
+    """The start rows of ManoHand.fit_sequence(init="frames") from per-frame rows [F, 16 + ncomps]: a frame without data
+    (has_data [F] bool False) takes the row of the nearest earlier frame of its sequence that has data, in a leading gap the nearest
+    later one; a sequence without any data keeps its rows.  share_betas: every row's betas becomes the mean over its sequence's
+    frames that have data (zeros where there are none).  offsets: host integers [S + 1].  torch operations on `rows`' device, no
+    host read."""
+    F, dev = rows.shape[0], rows.device
+    off = torch.as_tensor([int(v) for v in offsets], dtype=torch.int64)
+    lengths = (off[1:] - off[:-1]).to(dev)
+    seq = torch.repeat_interleave(torch.arange(len(offsets) - 1, device=dev), lengths, output_size=F)
+    start, end = off[:-1].to(dev)[seq], off[1:].to(dev)[seq]
+    idx = torch.arange(F, device=dev)
+    has = has_data.to(dev, torch.bool)
+    earlier = torch.cummax(torch.where(has, idx, torch.full_like(idx, -1)), 0).values            # the last frame with data at or before f
+    later = torch.flip(torch.cummin(torch.flip(torch.where(has, idx, torch.full_like(idx, F)), [0]), 0).values, [0])
+    src = torch.where(earlier >= start, earlier, torch.where(later < end, later, idx))
+    out = rows[src].clone()
+    if share_betas:
+        b0 = 3 + ncomps
+        m = has.to(rows.dtype)[:, None]
+        for a, b in zip(offsets[:-1], offsets[1:]):               # a sum per sequence: its order depends on the sequence alone
+            a, b = int(a), int(b)
+            out[a:b, b0:b0 + 10] = (rows[a:b, b0:b0 + 10] * m[a:b]).sum(0) / m[a:b].sum(0).clamp_min(1.0)
+    return out
 
 
 def axis_angle(R):

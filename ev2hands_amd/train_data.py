@@ -228,6 +228,35 @@ class RecordingSet:
             out[side] = hands[side].fit(j.to(torch.float32).contiguous(), weights=w.contiguous(), **fit_kwargs)
         return out
 
+    def fit_mano_sequence(self, hands, recordings=None, **fit_kwargs) -> dict:
+        """MANO rows for whole recordings: ManoHand.fit_sequence of `hands` on the frames of one recording (an index), several (a
+        list of indices, in that order) or all (None), every recording a sequence of its own (the offsets come from `joint_rows`).
+        A frame's hand whose joints are not all finite gets weight 0 throughout: its row is carried by the sequence's smoothness.
+        fit_kwargs: ManoHand.fit_sequence's but `offsets` (smooth, share_betas, init, ...; `weights` [sum F, 21] over the chosen
+        frames is multiplied in).  -> {'left': ManoSequenceFit, 'right': ManoSequenceFit}.  No host synchronisation."""
+        if recordings is None:
+            recordings = range(self.n_recordings)
+        recordings = [int(recordings)] if isinstance(recordings, (int, np.integer)) else [int(r) for r in recordings]
+        if not recordings or any(not 0 <= r < self.n_recordings for r in recordings):
+            raise ValueError(f"recordings are indices 0 .. {self.n_recordings - 1}")
+        if "offsets" in fit_kwargs:
+            raise ValueError("the offsets are the recordings' own")
+        spans = [(self.joint_rows[r], self.joint_rows[r + 1]) for r in recordings]
+        joints = self.joints if spans == [(self.joint_rows[r], self.joint_rows[r + 1]) for r in range(self.n_recordings)] else \
+            torch.cat([self.joints[a:b] for a, b in spans], 0)
+        offsets = [0]
+        for a, b in spans:
+            offsets.append(offsets[-1] + b - a)
+        extra = fit_kwargs.pop("weights", None)
+        out = {}
+        for h, side in enumerate(("left", "right")):
+            j = joints[:, h]
+            w = torch.isfinite(j).all(2).all(1).to(torch.float32)[:, None].expand(-1, 21)
+            if extra is not None:
+                w = w * extra.to(self.device, torch.float32)
+            out[side] = hands[side].fit_sequence(j.to(torch.float32).contiguous(), offsets=offsets, weights=w.contiguous(), **fit_kwargs)
+        return out
+
 
 class TrainingBatcherR:
     """The collated fine-tuning batch for items of a RecordingSet.  reference_quirks=True is the reference's item: augment_events

@@ -430,6 +430,50 @@ size_t ev2h_mano_fit_opts_size(void);      /* sizeof(ev2h_mano_fit_opts), for th
 int ev2h_mano_fit(const ev2h_mano_consts* c, const float* params0, int ldp, int B, const float* targets, size_t targets_stride,
                   const float* weights, size_t weights_stride, const ev2h_mano_fit_opts* opts, double* params_out, size_t out_stride,
                   double* stats, int32_t* info, ev2h_stream_t stream);
+typedef struct ev2h_mano_fit_seq_opts {
+    double lam_pose;             /* >= 0: prior weight on hand_pose, per frame                                         */
+    double lam_shape;            /* >= 0: prior weight on betas, per frame (a shared betas carries it once per frame)  */
+    double smooth[4];            /* >= 0: first-difference weights of global_orient, hand_pose, betas, transl          */
+    double mu0;                  /* >= 0: initial damping                                                             */
+    double ftol;                 /* >= 0: stop after an accepted step with cost - cost' <= ftol * cost                */
+    int32_t max_iters;           /* 1..64 solves per sequence                                                         */
+    int32_t free_mask;           /* as ev2h_mano_fit_opts.free_mask                                                   */
+    int32_t share_betas;         /* 1: one betas vector per sequence (smooth[2] must be 0); 0: every frame has its own */
+} ev2h_mano_fit_seq_opts;
+size_t ev2h_mano_fit_seq_opts_size(void);  /* sizeof(ev2h_mano_fit_seq_opts), for the binding's layout check */
+/* Bytes of ev2h_mano_fit_seq's device workspace for ncomps = K, n_frames frames in S sequences; 0 for arguments it refuses. */
+size_t ev2h_mano_fit_seq_workspace_bytes(int K, int n_frames, int S, int share_betas);
+/* Fit the parameter rows of whole sequences to 3-D joints (csrc/mano_fit.hip): one least-squares problem per sequence, float64 on
+ * the device, no host read.  offsets: HOST int32 [S + 1], offsets[0] == 0 and increasing: sequence s owns the frames
+ * offsets[s] .. offsets[s+1] - 1 (F_s >= 1) of params0 [n_frames][ldp] float32, targets [n_frames][21][3] (stride 0 = 63) and weights
+ * [n_frames][21] (stride 0 = 21, NULL = all 1), n_frames = offsets[S].
+ *   rows of a sequence's cost: per frame exactly ev2h_mano_fit's (data rows in mm by selection, ncomps rows sqrt(lam_pose) hand_pose_k,
+ *     10 rows sqrt(lam_shape) betas_k); for f >= 1 inside the sequence and every parameter i of group g the row
+ *     sqrt(smooth[g]) (x_f[i] - x_{f-1}[i]), in the parameters' own units.  No row crosses a sequence boundary.
+ *   share_betas = 1: the sequence has one betas vector, read from its first start row (the other rows' betas are ignored), replicated
+ *     into every output row; the per-frame unknowns are the other q = 6 + ncomps.  share_betas = 0: every frame has all P.
+ *   The normal equations are block-tridiagonal (frame blocks A_f, off-diagonal blocks -diag(smooth)) with a 10-column border for a
+ *     shared betas.  A frozen parameter has a zero row and column, diagonal 1 and g 0 (its temporal rows count in the cost only).
+ *   Levenberg-Marquardt per sequence, ev2h_mano_fit's rules: D_ii = H_ii where positive else 1 (H's diagonal with the temporal
+ *     terms), block Cholesky of H + mu D down the frames and through the border's Schur complement, a pivot that is not finite or
+ *     not positive is a rejected step; accept on cost' finite and < cost with mu <- max(mu / 10, 1e-12), else mu <- min(10 mu, 1e12);
+ *     a rejected step reuses the linearisation; every solve is an iteration; stop after an accepted step with
+ *     cost - cost' <= ftol * cost, at cost == 0, at max_iters.
+ * The host issues 2 + 4 * max_iters launches (cost and decide of the start rows; then linearise per frame, sweep per sequence,
+ * trial cost per frame, decide per sequence); a kernel of a finished sequence leaves at once.
+ * out_rows [n_frames][P] float64: the last accepted rows.  per_frame_cost [n_frames]: the data-plus-prior cost of each frame there.
+ * stats [S][4] = {cost at the start, final cost, final mu, max|g| of the last linearisation}, info [S][2] = {iterations, status}:
+ * 0 converged, 1 max_iters reached, 2 a non-finite start value that is read or a non-finite target of positive weight anywhere in
+ * the sequence (its out_rows = params0 widened, per_frame_cost NaN, stats {NaN, NaN, mu0, NaN}, 0 iterations).
+ * workspace: device memory of at least ev2h_mano_fit_seq_workspace_bytes, 8-byte aligned; nothing is allocated here.
+ * No atomics, fixed summation orders: the same call gives the same bytes, and a sequence's outputs depend on that sequence's
+ * inputs and opts alone, whatever else shares the launch.
+ * EV2H_ERR_ARG before any launch: what ev2h_mano_fit refuses, S < 1, offsets[0] != 0 or offsets not increasing, a negative or
+ * non-finite smooth, smooth[2] != 0 with share_betas, share_betas outside 0 / 1, a null or too small workspace, a null output. */
+int ev2h_mano_fit_seq(const ev2h_mano_consts* c, const float* params0, int ldp, const int32_t* offsets, int S, const float* targets,
+                      size_t targets_stride, const float* weights, size_t weights_stride, const ev2h_mano_fit_seq_opts* opts,
+                      void* workspace, size_t workspace_bytes, double* out_rows, double* per_frame_cost, double* stats, int32_t* info,
+                      ev2h_stream_t stream);
 
 /* ---- event window -> [5, N] tensor (next row 8f-1; dataset/evaluation_stream.py:187-225, ev2hands_r.py:108-159, erpc.py:169-249) ---- */
 /* Per-pixel accumulation + np.nonzero-order compaction of B ragged windows.  events: device float64 rows of ev_stride (>= 4)
@@ -1235,6 +1279,14 @@ int ev2h_dbg_attn_simfold_partials(const float* zpart, int rows_per_partial, con
                                    const float* w4t_right, const float* b4_left, const float* b4_right, float* sim, ev2h_stream_t stream);
 int ev2h_dbg_attn_context_rows16(const float* sim, const void* value16, int ldv, int B, int N, float* hf8, uint32_t* hf_amax,
                                  int amax_hand_stride, const float* value_unscale, const float* vscale, ev2h_stream_t stream);
+/* ev2h_dbg_mano_fit_seq_sweeps, csrc/mano_fit.hip: ev2h_mano_fit_seq's arguments and checks, but the launches are the start rows'
+ * cost and decide, ONE linearisation and then n_sweeps (0..64) launches of the sweep kernel on it (a sweep reads the blocks and the
+ * damping and writes factors and trial rows, so every launch does the same work).  out_rows = the start rows.  For
+ * tools/mano_fit_seq_timing.py, which times the sweep kernel alone with it. */
+int ev2h_dbg_mano_fit_seq_sweeps(const ev2h_mano_consts* c, const float* params0, int ldp, const int32_t* offsets, int S, const float* targets,
+                                 size_t targets_stride, const float* weights, size_t weights_stride, const ev2h_mano_fit_seq_opts* opts,
+                                 void* workspace, size_t workspace_bytes, double* out_rows, double* per_frame_cost, double* stats,
+                                 int32_t* info, ev2h_stream_t stream, int n_sweeps);
 
 #ifdef __cplusplus
 }
