@@ -8,6 +8,7 @@
 // same bytes, and window b's output depends on window b's inputs and the coefficient arguments only.
 #include "common.hpp"
 #include "ev2hands_hip.h"
+#include "mano_f64.hpp"
 
 namespace {
 
@@ -23,20 +24,6 @@ struct ManoBP {
     double* g_params; size_t gp_stride;
     int accumulate;
 };
-
-__constant__ int c_bw_joint_reorder[21] = {0, 13, 14, 15, 16, 1, 2, 3, 17, 4, 5, 6, 18, 10, 11, 12, 19, 7, 8, 9, 20};
-
-// G[k] = G[par] * [R_k | J_k - J_par] on rows of [R | t]
-__device__ __forceinline__ void chain_step(const double* P, const double* R, const double* Jk, const double* Jp, double* G) {
-    const double d[3] = {Jk[0] - Jp[0], Jk[1] - Jp[1], Jk[2] - Jp[2]};
-#pragma unroll
-    for (int r = 0; r < 3; ++r) {
-        const double p0 = P[4 * r], p1 = P[4 * r + 1], p2 = P[4 * r + 2];
-#pragma unroll
-        for (int c = 0; c < 3; ++c) G[4 * r + c] = fma(p2, R[6 + c], fma(p1, R[3 + c], p0 * R[c]));
-        G[4 * r + 3] = fma(p2, d[2], fma(p1, d[1], p0 * d[0])) + P[4 * r + 3];
-    }
-}
 
 // One workgroup per window.  The forward chain in float64, then backwards: outputs -> skinning -> A -> (G, J) -> kinematic chain ->
 // blend shapes -> betas, Rodrigues, PCA map.
@@ -69,7 +56,7 @@ __global__ __launch_bounds__(MB_THREADS) void mano_backward_kernel(ManoBP p) {
     } else if (tid >= 128 && tid < 128 + NB) {
         s_coef[tid - 128] = (double)betas[tid - 128];
     } else if (tid >= 192 && tid < 192 + 21) {
-        const int pos = tid - 192, src = c_bw_joint_reorder[pos];
+        const int pos = tid - 192, src = c_mano_reorder[pos];
         const double* gj = p.g_joints ? p.g_joints + (size_t)b * p.gj_stride + pos * 3 : nullptr;
 #pragma unroll
         for (int c = 0; c < 3; ++c) {
@@ -78,45 +65,13 @@ __global__ __launch_bounds__(MB_THREADS) void mano_backward_kernel(ManoBP p) {
         }
     }
     __syncthreads();
-    // Rodrigues, quaternion route, theta + 1e-8 inside the norm
-    if (tid < NJ) {
-        const double x = s_pose[3 * tid], y = s_pose[3 * tid + 1], z = s_pose[3 * tid + 2];
-        const double ex = x + 1e-8, ey = y + 1e-8, ez = z + 1e-8;
-        const double ang = sqrt(ex * ex + ey * ey + ez * ez);
-        const double ha = ang * 0.5, cs = cos(ha), sn = sin(ha);
-        double qw = cs, qx = sn * (x / ang), qy = sn * (y / ang), qz = sn * (z / ang);
-        const double qn = sqrt(qw * qw + qx * qx + qy * qy + qz * qz);
-        qw /= qn; qx /= qn; qy /= qn; qz /= qn;
-        double* R = s_R[tid];
-        R[0] = qw * qw + qx * qx - qy * qy - qz * qz; R[1] = 2 * qx * qy - 2 * qw * qz; R[2] = 2 * qw * qy + 2 * qx * qz;
-        R[3] = 2 * qw * qz + 2 * qx * qy; R[4] = qw * qw - qx * qx + qy * qy - qz * qz; R[5] = 2 * qy * qz - 2 * qw * qx;
-        R[6] = 2 * qx * qz - 2 * qw * qy; R[7] = 2 * qw * qx + 2 * qy * qz; R[8] = qw * qw - qx * qx - qy * qy + qz * qz;
-    }
+    if (tid < NJ) mano_rotation(&s_pose[3 * tid], s_R[tid]);
     __syncthreads();
     if (tid < NP) {
         const int e = tid % 9;
         s_coef[NB + tid] = s_R[1 + tid / 9][e] - ((e == 0 || e == 4 || e == 8) ? 1.0 : 0.0);
     }
-    // kinematic chain: one thread per finger walks its three joints down from the root
-    if (tid >= 192 && tid < 192 + 5) {
-        const int f = tid - 192;
-        double P[12], G[12];
-#pragma unroll
-        for (int r = 0; r < 3; ++r) {
-            P[4 * r] = s_R[0][3 * r]; P[4 * r + 1] = s_R[0][3 * r + 1]; P[4 * r + 2] = s_R[0][3 * r + 2]; P[4 * r + 3] = s_J[0][r];
-        }
-        if (f == 0) {
-#pragma unroll
-            for (int e = 0; e < 12; ++e) s_G[0][e] = P[e];
-        }
-#pragma unroll
-        for (int lev = 1; lev <= 3; ++lev) {
-            const int k = 3 * f + lev, par = lev == 1 ? 0 : k - 1;
-            chain_step(P, s_R[k], s_J[k], s_J[par], G);
-#pragma unroll
-            for (int e = 0; e < 12; ++e) { s_G[k][e] = G[e]; P[e] = G[e]; }
-        }
-    }
+    if (tid >= 192 && tid < 192 + 5) finger_chain(tid - 192, s_R, s_J, s_G);
     __syncthreads();
     if (tid < NJ) {                                               // A = G with t - R_G j
 #pragma unroll

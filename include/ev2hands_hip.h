@@ -443,7 +443,7 @@ typedef struct ev2h_mano_fit_seq_opts {
 size_t ev2h_mano_fit_seq_opts_size(void);  /* sizeof(ev2h_mano_fit_seq_opts), for the binding's layout check */
 /* Bytes of ev2h_mano_fit_seq's device workspace for ncomps = K, n_frames frames in S sequences; 0 for arguments it refuses. */
 size_t ev2h_mano_fit_seq_workspace_bytes(int K, int n_frames, int S, int share_betas);
-/* Fit the parameter rows of whole sequences to 3-D joints (csrc/mano_fit.hip): one least-squares problem per sequence, float64 on
+/* Fit the parameter rows of whole sequences to 3-D joints (csrc/mano_fit_seq.hip): one least-squares problem per sequence, float64 on
  * the device, no host read.  offsets: HOST int32 [S + 1], offsets[0] == 0 and increasing: sequence s owns the frames
  * offsets[s] .. offsets[s+1] - 1 (F_s >= 1) of params0 [n_frames][ldp] float32, targets [n_frames][21][3] (stride 0 = 63) and weights
  * [n_frames][21] (stride 0 = 21, NULL = all 1), n_frames = offsets[S].
@@ -1279,7 +1279,7 @@ int ev2h_dbg_attn_simfold_partials(const float* zpart, int rows_per_partial, con
                                    const float* w4t_right, const float* b4_left, const float* b4_right, float* sim, ev2h_stream_t stream);
 int ev2h_dbg_attn_context_rows16(const float* sim, const void* value16, int ldv, int B, int N, float* hf8, uint32_t* hf_amax,
                                  int amax_hand_stride, const float* value_unscale, const float* vscale, ev2h_stream_t stream);
-/* ev2h_dbg_mano_fit_seq_sweeps, csrc/mano_fit.hip: ev2h_mano_fit_seq's arguments and checks, but the launches are the start rows'
+/* ev2h_dbg_mano_fit_seq_sweeps, csrc/mano_fit_seq.hip: ev2h_mano_fit_seq's arguments and checks, but the launches are the start rows'
  * cost and decide, ONE linearisation and then n_sweeps (0..64) launches of the sweep kernel on it (a sweep reads the blocks and the
  * damping and writes factors and trial rows, so every launch does the same work).  out_rows = the start rows.  For
  * tools/mano_fit_seq_timing.py, which times the sweep kernel alone with it. */

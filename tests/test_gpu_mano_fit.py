@@ -1,5 +1,5 @@
-"""GPU: the MANO fit (csrc/mano_fit.hip: ev2h_mano_joints_jacobian, ev2h_mano_fit; ManoHand.joints_jacobian, ManoHand.fit,
-RecordingSet.fit_mano).
+"""GPU: the MANO fit (csrc/mano_fit.hip, its steps in csrc/mano_fit_steps.hpp: ev2h_mano_joints_jacobian, ev2h_mano_fit;
+ManoHand.joints_jacobian, ManoHand.fit, RecordingSet.fit_mano).
 
 The yardstick is tests/ref_mano_fit.py: the float64 oracle layer on the packed constants, autograd's Jacobian and the same
 Levenberg-Marquardt loop on the CPU, in two solve variants A (Cholesky) and B (torch.linalg.solve).  Bounds:
