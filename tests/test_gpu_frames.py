@@ -16,6 +16,7 @@ import torch
 
 import ref_frames
 import ref_render as RR
+from ref_render_edges import compare_with_reference
 from test_frames_cpu import load_cases
 
 pytestmark = pytest.mark.gpu
@@ -53,35 +54,6 @@ def posed_hands(kind: str, B: int, seed: int):
 def reference_window(vl, vr, fl, fr):
     verts, faces, normals = RR.concat_hands(vl, vr, fl, fr)
     return RR.render(verts, faces, normals, W, H)
-
-
-def compare_with_reference(ref, rgb, depth, fid, cap, label):
-    """the comparison of the module docstring for one window; prints every figure before it asserts"""
-    F = 2 * 1538
-    cov = ref["face_id"] >= 0
-    dec = RR.decided(ref)
-    ncov = int(cov.sum())
-    undecided = int((cov & ~dec).sum())
-    same_face = fid[dec] == ref["face_id"][dec]
-    both = dec & cov & (fid == ref["face_id"])
-    rel = np.abs(depth[both].astype(np.float64) - ref["depth"][both]) / ref["depth"][both]
-    dcol = np.abs(rgb[both].astype(np.int32) - ref["rgb"][both].astype(np.int32))
-    und = ~dec
-    keys = (np.flatnonzero(und).astype(np.int64)) * F + fid[und].astype(np.int64)
-    ok_und = (fid[und] < 0) | np.isin(keys, ref["near"])
-    print(f"{label}: covered {ncov}, undecided {undecided} ({100.0 * undecided / max(ncov, 1):.2f} % of covered), decided pixels with another "
-          f"face {int((~same_face).sum())}, max relative depth error {rel.max() if rel.size else 0.0:.3e}, colour differences "
-          f"{int((dcol.max(-1) > 0).sum()) if dcol.size else 0} (max {int(dcol.max()) if dcol.size else 0} levels), undecided pixels outside "
-          f"the listed faces {int((~ok_und).sum())}")
-    assert ncov >= 2000
-    assert undecided <= cap * ncov
-    assert same_face.all()
-    assert rel.size and rel.max() <= 1e-5
-    assert dcol.max() <= 1
-    assert ok_und.all()
-    bg = dec & ~cov
-    assert (depth[bg] == 0).all() and (rgb[bg] == 0).all()
-    assert (rgb[..., :2] == 0).all()
 
 
 # ------------------------------------------------------------------------------------------------------------ panels 1 and 2
@@ -168,7 +140,7 @@ def test_render_matches_the_float64_renderer_on_surface_hands():
     rgb, depth, fid = rgb.cpu().numpy(), depth.cpu().numpy(), fid.cpu().numpy()
     for b in range(4):
         ref = reference_window(vl[b].numpy(), vr[b].numpy(), fl, fr_)
-        compare_with_reference(ref, rgb[b], depth[b], fid[b], 0.05, f"surface window {b}")
+        compare_with_reference(ref, rgb[b], depth[b], fid[b], 0.05, f"surface window {b}", 2000, 2 * 1538)
         assert (fid[b] >= 1538).any() and ((fid[b] >= 0) & (fid[b] < 1538)).any()          # both hands in view
 
 
@@ -178,7 +150,7 @@ def test_render_matches_the_float64_renderer_on_triangle_soup():
     fr = _frames((fl, fr_))
     rgb, depth, fid = fr.render(vl.to(DEV), vr.to(DEV), return_buffers=True)
     ref = reference_window(vl[0].numpy(), vr[0].numpy(), fl, fr_)
-    compare_with_reference(ref, rgb[0].cpu().numpy(), depth[0].cpu().numpy(), fid[0].cpu().numpy(), 0.10, "soup window")
+    compare_with_reference(ref, rgb[0].cpu().numpy(), depth[0].cpu().numpy(), fid[0].cpu().numpy(), 0.10, "soup window", 2000, 2 * 1538)
 
 
 def test_render_known_answers_on_the_device():
