@@ -102,7 +102,7 @@ W_EQUALIZED, W_UNEQUALIZED_OK = 1, 2
 # ev2h_segmentation_score_backward, ev2h_loss_terms_backward, ev2h_collision_penalty_backward), and for the test hooks (ev2h_dbg_*),
 # and for the fitting exports (ev2h_mano_joints_jacobian, ev2h_mano_fit, ev2h_mano_fit_opts_size, ev2h_mano_fit_seq,
 # ev2h_mano_fit_seq_opts_size, ev2h_mano_fit_seq_workspace_bytes), and for the event simulator
-# (ev2h_esim_scratch_bytes, ev2h_esim_step, ev2h_esim_compose), and for the pose track (ev2h_pose_track_prepare, ev2h_pose_track_rows,
+# (ev2h_esim_scratch_bytes, ev2h_esim_step, ev2h_esim_compose, ev2h_esim_shade), and for the pose track (ev2h_pose_track_prepare, ev2h_pose_track_rows,
 # ev2h_pose_track_hand_size).
 ABI_VERSION = 8     # 8: EV2H_PREC_F16 (one fp16 plane with f16x2's range machinery); 3: F16X2 range records; 4: ev2h_fp_mlp, ev2h_weights.fp1m; 5: window strides of the outputs; 6: ev2h_pack_weights, ev2h_weights.flags; 7: ev2h_sa_desc.xyz_out
 
@@ -162,7 +162,7 @@ EXPORTS = [
     "ev2h_mano_backward", "ev2h_segmentation_score_backward", "ev2h_loss_terms_backward", "ev2h_collision_penalty_backward",
     "ev2h_mano_joints_jacobian", "ev2h_mano_fit", "ev2h_mano_fit_opts_size",
     "ev2h_mano_fit_seq", "ev2h_mano_fit_seq_opts_size", "ev2h_mano_fit_seq_workspace_bytes",
-    "ev2h_esim_scratch_bytes", "ev2h_esim_step", "ev2h_esim_compose",
+    "ev2h_esim_scratch_bytes", "ev2h_esim_step", "ev2h_esim_compose", "ev2h_esim_shade",
     "ev2h_pose_track_prepare", "ev2h_pose_track_rows", "ev2h_pose_track_hand_size",
     # test hooks, not part of the stable interface (include/ev2hands_hip.h: "Test hooks"; ev2hands_amd/ops.py: *_rows16, dense_zsum, ...)
     "ev2h_dbg_fp_mlp_rows16", "ev2h_dbg_gemm_zsum_supported", "ev2h_dbg_gemm_zsum", "ev2h_dbg_attn_simfold_partials", "ev2h_dbg_attn_context_rows16",
@@ -285,6 +285,7 @@ def lib() -> C.CDLL:
     L.ev2h_esim_step.argtypes = [vp, ci, ci, ci, vp, ci, vp, vp, C.c_double, C.c_double, C.c_double, C.c_double, ci, ci, ci, vp, vp, vp, vp,
                                  ci, vp, ci, vp, C.c_size_t, vp]
     L.ev2h_esim_compose.argtypes = [vp, vp, vp, ci, ci, ci, ci, ci, ci, vp, vp]
+    L.ev2h_esim_shade.argtypes = [vp, vp, vp, C.c_size_t, vp, ci, vp, ci, ci, ci, ci] + [C.c_float] * 9 + [vp, ci, ci, C.c_uint64, vp, vp, vp, ci, vp, vp]
     L.ev2h_pose_track_hand_size.restype = C.c_size_t
     L.ev2h_pose_track_hand_size.argtypes = []
     L.ev2h_pose_track_prepare.argtypes = [vp, ci, vp, vp, vp, vp]

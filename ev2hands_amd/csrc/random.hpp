@@ -18,6 +18,14 @@
 //     next index is bounded(w2, i - (min_events - 1)), the reference's inclusive randint(0, i - 2048) at min_events = 2048
 //   stream 4, the polarity flips of an augmented fine-tuning window (events.hip: FlipPolarity): row e of the window (e < 32768, counted
 //     from its first row) is flipped iff bit e & 31 of word (e >> 5) & 3 of block e >> 7 is set
+//   stream 5, the five point lights of a simulated frame (shade.hip: shade_lights_kernel; the reference's generate_train_lights,
+//     HandSimulator/utils.py:286-313, as a pure function of (seed, global frame)): window_id = the global frame number's low 32 bits.
+//     light k = 0 .. 4, block 2k: the radiant intensity is 1 + (w0 >> 30), white; w1, w2, w3 give the jitter of x, y, z.  A uniform is
+//     (word >> 8) * 2^-24, a float32 in [0, 1) (exact); the jitter is uniform / 10.  Lights 0, 1, 2 stand at (0, -1, 1), (0, 1, 1),
+//     (1, 1, 2) + jitter.  Lights 3 and 4 take w0, w1, w2 of block 2k + 1 as three more uniforms u and stand at (2 u - 1) * 2 + jitter
+//     per axis.  Every arithmetic step is one float32 rounding; the position is then mapped (x, y, z) -> (x, -y, -z) into the
+//     rasteriser's camera frame.  Blocks 1, 3, 5 and word 3 of blocks 7 and 9 are not used.  These are the project's own draws, not
+//     numpy's or Python's.
 //   a 32-bit word u becomes an index below M by multiply-shift, (u * M) >> 32 in 64 bits.  There is NO rejection step, so the
 //   indices are not exactly uniform: some values are hit by ceil(2^32 / M) words and the others by floor(2^32 / M), a relative
 //   bias of at most M / 2^32 -- below 7.7e-6 for M <= 32768 (the largest table a window can have).
@@ -30,7 +38,7 @@ namespace ev2h_random {
 
 constexpr uint32_t PHILOX_M0 = 0xD2511F53u, PHILOX_M1 = 0xCD9E8D57u;        // round multipliers
 constexpr uint32_t PHILOX_W0 = 0x9E3779B9u, PHILOX_W1 = 0xBB67AE85u;        // key increments (Weyl sequence)
-constexpr uint32_t STREAM_SAMPLE = 0, STREAM_FPS = 1, STREAM_AUGMENT = 2, STREAM_FINETUNE = 3, STREAM_FLIP = 4;
+constexpr uint32_t STREAM_SAMPLE = 0, STREAM_FPS = 1, STREAM_AUGMENT = 2, STREAM_FINETUNE = 3, STREAM_FLIP = 4, STREAM_LIGHTS = 5;
 
 struct u32x4 { uint32_t v[4]; };
 
@@ -60,6 +68,9 @@ __device__ __forceinline__ uint32_t bounded(uint32_t u, uint32_t bound) { return
 __device__ __forceinline__ double unit_double(uint32_t w0, uint32_t w1) {
     return (double)(((uint64_t)(w0 >> 5) << 26) | (uint64_t)(w1 >> 6)) * 0x1p-53;
 }
+
+// a word -> a float32 in [0, 1) with 24 random bits (exact)
+__device__ __forceinline__ float unit_float(uint32_t w) { return (float)(w >> 8) * 0x1p-24f; }
 
 // word w (0..3) of a block by selects, not an indexed (scratch) read
 __device__ __forceinline__ uint32_t block_word(const u32x4& b, uint32_t w) { return w == 0 ? b.v[0] : w == 1 ? b.v[1] : w == 2 ? b.v[2] : b.v[3]; }

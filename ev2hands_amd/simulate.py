@@ -17,11 +17,14 @@ Ev2HandSDataset expects.
 What is the PROJECT'S OWN: timestamps="interpolated" is ESIM's rule (linear crossing times between two frames) applied to this
 simulator's memory frame, stated in include/ev2hands_hip.h and tests/ref_esim.py; the reference's ColorESIM calls esim_torch, a CUDA
 extension that is not part of the reference tree, so parity with it is UNPINNED.  The frames `step` feeds the generator are DemoFrames'
-render (csrc/render.hip, itself unpinned against pyrender) coloured with one `hand_color` over a fixed `background`: not pyrender with
-UV textures, random lights and background images.  The labels are the render's own face_id (0 background, 1 left, 2 right), which is
+render (csrc/render.hip, itself unpinned against pyrender) coloured with one `hand_color` over a fixed `background`; with
+`appearance=` (appearance.HandAppearance) they are shaded instead by csrc/shade.hip: per-vertex colours, the reference's metallic-roughness
+material, ambient 0.1, five point lights drawn again for every frame (or a table of yours) and the reference's grey-level paste over
+`background` -- the project's own rule (tests/ref_shade.py), not pyrender's shader or its output encoding.  The labels are the render's own face_id (0 background, 1 left, 2 right), which is
 what the reference's segmentation render encodes.
 
-NOT provided: UV textures, lights, background image sets, the InterHand readers and .h5 / pickle writing.  The rows `step` takes are
+NOT provided: reading texture or background files (vertex colours and one background image are arguments), the forearm cylinders, the
+5 mm per-frame jitter of generate_mesh and augment_mano_sequence, shadows, the InterHand readers and .h5 / pickle writing.  The rows `step` takes are
 camera-space, as camera_hand_info is; pose_track.PoseTrack makes them from keyframes (interpolation, AA -> PCA, camera transform).
 
 Every buffer is allocated in `begin`: `step_images` and `step` synchronise nothing, allocate nothing and read nothing back; `finish`
@@ -37,6 +40,7 @@ import torch
 from . import _lib
 from ._lib import _dev_tensor
 from .events import OUTPUT_HEIGHT, OUTPUT_WIDTH, EventTableS
+from .appearance import REFERENCE_LIGHTS, HandAppearance
 from .frames import DemoFrames
 
 BACKGROUND_GREY = 159                      # color_event_simulator.py:151: the grey the reference's memory frame starts from
@@ -58,12 +62,14 @@ class EventSimulatorS:
     0.4, 0.4, 1e-6; both thresholds must exceed 2 eps).  timestamps: "frame" | "scaled" | "interpolated" (module docstring).
     capacity: rows of the table; max_annotations: entries of annotation_frame; chunk: the most frames one step takes;
     max_per_pixel (<= 127): the bound of a pixel's events in one frame; max_events_per_frame (<= 8192): the interpolated order's
-    sort capacity.  background: uint8 [H, W, 3] (default all 159); hand_color: RGB.  f, cx, cy: the camera (DemoFrames' defaults)."""
+    sort capacity.  background: uint8 [H, W, 3] (default all 159); hand_color: RGB.  f, cx, cy: the camera (DemoFrames' defaults).
+    appearance: an appearance.HandAppearance -- `render` / `step` / `step_track` then shade the frames with it (hand_color is not used);
+    None: the flat colouring."""
 
     def __init__(self, device, hands, fps: float = 1000, threshold_pos: float = 0.4, threshold_neg: float = 0.4, eps: float = 1e-6,
                  timestamps: str = "interpolated", width: int = OUTPUT_WIDTH, height: int = OUTPUT_HEIGHT, capacity: int = 4_000_000,
                  chunk: int = 64, background=None, hand_color=(198, 134, 66), max_per_pixel: int = 64, max_events_per_frame: int = 8192,
-                 max_annotations: int = 65536, f: float | None = None, cx: float | None = None, cy: float | None = None):
+                 max_annotations: int = 65536, f: float | None = None, cx: float | None = None, cy: float | None = None, appearance=None):
         self.device = torch.zeros(0, device=device).device
         if self.device.type != "cuda":
             raise RuntimeError("EventSimulatorS runs on the GPU only (there is no CPU fallback)")
@@ -91,6 +97,12 @@ class EventSimulatorS:
         if hands is not None:
             self.frames = DemoFrames(self.device, hands["left"].faces, hands["right"].faces, self.w, self.h, f=f, cx=cx, cy=cy, max_batch=self.chunk)
             self.nf = self.frames.nf
+        self.appearance = appearance
+        if appearance is not None:
+            if hands is None:
+                raise ValueError("an appearance needs the hands it colours (hands=None renders nothing)")
+            if not isinstance(appearance, HandAppearance) or appearance.device != self.device or appearance.nv != self.frames.nv:
+                raise ValueError(f"appearance must be a HandAppearance on {self.device} with {self.frames.nv} colours per hand")
         self.table = torch.from_numpy(log_table()).to(self.device)
         self.scratch_bytes = int(_lib.lib().ev2h_esim_scratch_bytes(self.chunk, self.w, self.h, self.mode, self.mepf))
         if self.scratch_bytes == 0:
@@ -115,6 +127,9 @@ class EventSimulatorS:
             self._joints = torch.empty(2, F, 21, 3, device=dev, dtype=torch.float32)
             self._frame = torch.empty(F, H, W, 3, device=dev, dtype=torch.uint8)
             self._face_id = torch.empty(F, H, W, device=dev, dtype=torch.int32)
+            if self.appearance is not None:                                     # what the shading reads and the lights it draws
+                self._depth = torch.empty(F, H, W, device=dev, dtype=torch.float32)
+                self._light_table = torch.empty(F, REFERENCE_LIGHTS, 6, device=dev, dtype=torch.float32)
             self._track_rows = None                                             # what `step_track` has the track write
             if hasattr(self.hands["left"], "ncomps"):                           # (hands that hold faces only can render vertices, not rows)
                 P = 16 + self.hands["left"].ncomps
@@ -156,9 +171,10 @@ class EventSimulatorS:
                                              self._scratch.numel(), _lib.stream_handle()), "ev2h_esim_step")
         self.n_frames += F
 
-    def render(self, params_left, params_right, present=None):
+    def render(self, params_left, params_right, present=None, lights=None):
         """-> (rgb uint8 [F, H, W, 3], the render's frame, face_id): what `step` feeds the generator, views of buffers allocated in
-        `begin` that the next call overwrites"""
+        `begin` that the next call overwrites.  lights (with an appearance only): float32 [F, L, 6] on the device, this call's lights
+        per frame in place of the appearance's."""
         self._begun()
         if self.frames is None:
             raise RuntimeError("EventSimulatorS was built without hands: only step_images is available")
@@ -166,6 +182,8 @@ class EventSimulatorS:
         F = int(params_left.shape[0]) if torch.is_tensor(params_left) and params_left.dim() == 2 else 0
         if not 1 <= F <= self.chunk:
             raise ValueError(f"a step takes 1 .. {self.chunk} frames")
+        if lights is not None and self.appearance is None:
+            raise ValueError("lights need an appearance (EventSimulatorS(appearance=...))")
         if present is not None:
             _dev_tensor(present, "present", torch.bool, (F, 2), self.device)
         for h, (side, prm) in enumerate((("left", params_left), ("right", params_right))):
@@ -178,17 +196,22 @@ class EventSimulatorS:
             if present is not None:
                 torch.where(present[:, h, None, None], v, self._behind, out=v)
             verts.append(v)
-        frame, _, face_id = self.frames.render(verts[0], verts[1], out=(self._frame[:F], None, self._face_id[:F]))
         rgb = self._rgb[:F]
+        if self.appearance is not None:
+            frame, depth, face_id = self.frames.render(verts[0], verts[1], out=(self._frame[:F], self._depth[:F], self._face_id[:F]))
+            self.appearance.shade(self.frames, depth, face_id, rgb, background=self.background, lights=lights, frame_counter=self.state,
+                                  light_table=self._light_table)
+            return rgb, frame, face_id
+        frame, _, face_id = self.frames.render(verts[0], verts[1], out=(self._frame[:F], None, self._face_id[:F]))
         r, g, b = self.hand_color
         _lib.check(_lib.lib().ev2h_esim_compose(frame.data_ptr(), face_id.data_ptr(), self.background.data_ptr(), F, self.w, self.h, r, g, b,
                                                 rgb.data_ptr(), _lib.stream_handle()), "ev2h_esim_compose")
         return rgb, frame, face_id
 
-    def step(self, params_left, params_right, present=None) -> None:
+    def step(self, params_left, params_right, present=None, lights=None) -> None:
         """params_* float32 [F, 16 + K] (global_orient | hand_pose | betas | transl, camera space), F <= chunk; present bool [F, 2]:
-        False drops that hand from that frame (it is moved behind the camera)."""
-        rgb, _, face_id = self.render(params_left, params_right, present)
+        False drops that hand from that frame (it is moved behind the camera); lights: as `render` takes them."""
+        rgb, _, face_id = self.render(params_left, params_right, present, lights)
         self.step_images(rgb, face_id=face_id)
 
     def step_track(self, track, f0: int, f1: int) -> None:

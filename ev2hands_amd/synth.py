@@ -360,3 +360,19 @@ def synth_mano_surface_assets(side: str, seed: int = 0) -> dict:
     base = synth_mano_assets(side, seed)
     return {"side": side, "v_template": v, "shapedirs": shapedirs, "posedirs": posedirs, "J_regressor": jr, "weights": w,
             "hands_components": base["hands_components"], "hands_mean": base["hands_mean"], "faces": faces, "parents": list(MANO_PARENTS)}
+
+
+def synth_vertex_colors(side: str, seed: int = 0, nv: int = MANO_NV) -> np.ndarray:
+    """uint8 [nv, 3] RGB: plausible per-vertex skin colours for simulate.EventSimulatorS(appearance=...) -- one skin tone per (side,
+    seed) between a light and a dark one, a smooth low-frequency change of brightness along the vertex list (a texture sampled at the
+    vertices varies slowly over the surface) and a few levels of per-vertex noise.  For tests and timing; the reference samples
+    texture files at the mesh's UV coordinates (HandSimulator/dataset/mano_texture.py:81-99), which this project does not read."""
+    tag = f"vertex_colors/{side}"
+    light, dark = np.array([224.0, 172.0, 138.0]), np.array([141.0, 85.0, 54.0])
+    tone = dark + (light - dark) * float(hash_uniform(tag + "/tone", (1,), seed)[0])
+    x = np.arange(nv) / max(nv - 1, 1)
+    amp = hash_normal(tag + "/amp", (4,), seed) * 0.06
+    ph = hash_uniform(tag + "/ph", (4,), seed) * 2 * np.pi
+    gain = 1.0 + sum(amp[k] * np.sin(2 * np.pi * (k + 1) * x + ph[k]) for k in range(4))
+    col = tone[None, :] * gain[:, None] + hash_normal(tag + "/noise", (nv, 3), seed) * 4.0
+    return np.clip(np.floor(col + 0.5), 0, 255).astype(np.uint8)

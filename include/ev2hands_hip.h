@@ -989,6 +989,52 @@ int ev2h_esim_step(const uint8_t* rgb, int n_frames, int width, int height, cons
  * The project's own colouring: the reference renders UV textures under random lights over background images. */
 int ev2h_esim_compose(const uint8_t* frame, const int32_t* face_id, const uint8_t* background, int n_frames, int width, int height,
                       int red, int green, int blue, uint8_t* rgb, ev2h_stream_t stream);
+/* The appearance model of the simulator's frames (csrc/shade.hip), in place of ev2h_esim_compose: per-vertex colours, a glTF 2.0
+ * metallic-roughness material under an ambient term and up to 8 point lights, pasted over a background.  It runs after
+ * ev2h_render_hands on the same chunk and reads what that call left: face_id [n_frames][height][width], depth (mm, the same shape)
+ * and the render scratch (per window and vertex (u, v, 1/z_mm, -, nx, ny, nz, -)); scratch_bytes must EQUAL
+ * ev2h_render_scratch_bytes(n_frames, nv).  faces [nfaces][3], (f, cx, cy): as given to ev2h_render_hands.  vertex_colors
+ * [2 nv][3] uint8 RGB, left hand then right.  rgb [n_frames][height][width][3] out.
+ *
+ * The rule is the project's own (tests/ref_shade.py is its float64 statement; parity with pyrender's shader is unpinned, as the
+ * rasteriser's is).  The reference: HandSimulator/utils.py:225-230 (the material), :286-313 (the lights), :264-284 (the paste),
+ * :323 (ambient 0.1).  Per pixel (r, c) with face_id >= 0, in float32, one rounding per operation:
+ *   weights   wa = E_bc w_a, wb = E_ca w_b, wc = E_ab w_c: the edge functions of tests/ref_render.py at the sample (c + 0.5, r + 0.5)
+ *             times the vertices' 1/z_mm
+ *   normal    n = wa n_a + wb n_b + wc n_c, normalised; |n|^2 < 1e-30: the pixel is ambient only
+ *   position  z = depth_mm / 1000,  P = ((c + 0.5 - cx) z / f, (r + 0.5 - cy) z / f, z),  v = -P / |P|
+ *   two-sided n.v < 0 turns n round; n.v = 0 leaves the specular term out
+ *   albedo    base = base_color_factor * ((wa c_a + wb c_b + wc c_c) / (wa + wb + wc)) / 255 per channel
+ *   material  alpha = roughness^2,  F0 = 0.04 + (base - 0.04) metallic,  c_diff = base * (0.96 (1 - metallic))
+ *   a light   (position in metres in the rasteriser's camera frame, RGB radiant intensity)  with l = (pos - P) / d and n.l > 0:
+ *             h = (l + v) / |l + v| (|l + v|^2 < 1e-30 or d = 0: the light adds nothing),
+ *             F = F0 + (1 - F0) max(0, 1 - v.h)^5,  D = alpha^2 / (pi ((n.h)^2 (alpha^2 - 1) + 1)^2),
+ *             Vis = 0.5 / (n.l sqrt((n.v)^2 (1 - alpha^2) + alpha^2) + n.v sqrt((n.l)^2 (1 - alpha^2) + alpha^2)),
+ *             it adds ((1 - F) c_diff / pi + F D Vis) * intensity / d^2 * n.l
+ *   value     base * ambient + the lights' sum, clamped to [0, 1], written as (uint8)(x * 255 + 0.5).  There is NO transfer curve:
+ *             the byte is the linear value (pyrender's output encoding is not reproduced).
+ * Lights: `lights` [n_frames or 1][n_lights][6] float32 (lights_per_frame 1 or 0), 0 <= n_lights <= 8; or `lights` null, n_lights 5:
+ * the draw of csrc/random.hpp stream 5 for (seed, *frame_counter + frame) is written to light_table [n_frames][5][6] by a first
+ * small launch and used from there -- frame_counter is a device int64 (the simulator's state word EV2H_ESIM_STATE_FRAMES), nothing is
+ * read back.  Composition, on the rounded bytes: background null -- the render stands on black (a pixel with face_id < 0 is 0);
+ * otherwise a pixel keeps its render when, mask_rule 1, grey = (1868 r + 9617 g + 4899 b + 8192) >> 14 is above 10 (the reference's
+ * cv2.cvtColor(rgb, COLOR_BGR2GRAY) + threshold(10) of augment_background: OpenCV's 14-bit constants B2Y 1868, G2Y 9617, R2Y 4899
+ * applied to an RGB image, so red carries 1868; restated from public OpenCV, parity with cv2 unpinned; an uncovered pixel's render is
+ * black), or when, mask_rule 0, face_id >= 0; every other pixel is background [height][width][3].  A dark hand pixel shows the
+ * background through under mask_rule 1, as upstream.
+ *
+ * One lane per pixel in the rasteriser's 16 x 16 tiles; a wave without a covered lane only copies background; no atomics, every
+ * pixel is a function of its own frame: any split of a sequence into calls gives the same bytes.  Allocates nothing, does not
+ * synchronise.  EV2H_ERR_ARG before any launch: a null pointer (background may be null; lights null needs frame_counter and
+ * light_table), n_lights outside 0 .. 8 (or not 5 for the draw), lights_per_frame outside 0 .. 1, scratch_bytes !=
+ * ev2h_render_scratch_bytes(n_frames, nv), a misaligned scratch, roughness outside (0, 1], metallic or base_color_factor outside
+ * [0, 1], a negative or non-finite ambient, f <= 0, a non-finite camera, n_frames outside 1 .. 4096, width or height outside
+ * 1 .. 4096, width * height > 2^22, 2 nv outside 2 .. 2048, nfaces < 1, mask_rule outside 0 .. 1. */
+int ev2h_esim_shade(const int32_t* face_id, const float* depth, const void* render_scratch, size_t scratch_bytes, const int32_t* faces,
+                    int nfaces, const uint8_t* vertex_colors, int n_frames, int nv, int width, int height, float f, float cx, float cy,
+                    float base_color_factor, float metallic, float roughness, float ambient_r, float ambient_g, float ambient_b,
+                    const float* lights, int n_lights, int lights_per_frame, uint64_t seed, const int64_t* frame_counter,
+                    float* light_table, const uint8_t* background, int mask_rule, uint8_t* rgb, ev2h_stream_t stream);
 
 /* ---- MANO keyframes -> the simulator's pose rows (csrc/pose_track.hip; HandSimulator/dataset/utils.py:11-113, interhand.py:69-158) ----
  * A hand's track is L keyframe rows keys [L][61] float64 = pose(48: 16 axis-angle joints) | shape(10) | trans(3) at the uniform knots
