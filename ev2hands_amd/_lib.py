@@ -102,7 +102,8 @@ W_EQUALIZED, W_UNEQUALIZED_OK = 1, 2
 # ev2h_segmentation_score_backward, ev2h_loss_terms_backward, ev2h_collision_penalty_backward), and for the test hooks (ev2h_dbg_*),
 # and for the fitting exports (ev2h_mano_joints_jacobian, ev2h_mano_fit, ev2h_mano_fit_opts_size, ev2h_mano_fit_seq,
 # ev2h_mano_fit_seq_opts_size, ev2h_mano_fit_seq_workspace_bytes), and for the event simulator
-# (ev2h_esim_scratch_bytes, ev2h_esim_step, ev2h_esim_compose, ev2h_esim_shade), and for the pose track (ev2h_pose_track_prepare, ev2h_pose_track_rows,
+# (ev2h_esim_scratch_bytes, ev2h_esim_step, ev2h_esim_scratch_bytes_wide, ev2h_esim_step_wide, ev2h_esim_compose, ev2h_esim_shade),
+# and for the pose track (ev2h_pose_track_prepare, ev2h_pose_track_rows,
 # ev2h_pose_track_hand_size).
 ABI_VERSION = 8     # 8: EV2H_PREC_F16 (one fp16 plane with f16x2's range machinery); 3: F16X2 range records; 4: ev2h_fp_mlp, ev2h_weights.fp1m; 5: window strides of the outputs; 6: ev2h_pack_weights, ev2h_weights.flags; 7: ev2h_sa_desc.xyz_out
 
@@ -133,6 +134,7 @@ class PoseTrackHand(C.Structure):
 POSE_TRACK_KEY, POSE_TRACK_COEF, POSE_TRACK_PARTS = 61, 14, 112      # EV2H_POSE_TRACK_*
 ESIM_MODES = {"frame": 0, "scaled": 1, "interpolated": 2}      # EV2H_ESIM_FRAME, _FRAME_SCALED, _INTERPOLATED
 ESIM_OVER_CAPACITY, ESIM_LOOP_BOUND, ESIM_OVER_SORT = 1, 2, 4     # the status bits of ev2h_esim_step's state[3]
+ESIM_SORT_MAX, ESIM_SORT_WIDE_MAX = 8192, 1 << 20               # max_events_per_frame of ev2h_esim_step and of ev2h_esim_step_wide
 FIT_GROUPS = ("global_orient", "hand_pose", "betas", "transl")      # bits 0..3 of ev2h_mano_fit_opts.free_mask
 
 
@@ -162,11 +164,11 @@ EXPORTS = [
     "ev2h_mano_backward", "ev2h_segmentation_score_backward", "ev2h_loss_terms_backward", "ev2h_collision_penalty_backward",
     "ev2h_mano_joints_jacobian", "ev2h_mano_fit", "ev2h_mano_fit_opts_size",
     "ev2h_mano_fit_seq", "ev2h_mano_fit_seq_opts_size", "ev2h_mano_fit_seq_workspace_bytes",
-    "ev2h_esim_scratch_bytes", "ev2h_esim_step", "ev2h_esim_compose", "ev2h_esim_shade",
+    "ev2h_esim_scratch_bytes", "ev2h_esim_step", "ev2h_esim_scratch_bytes_wide", "ev2h_esim_step_wide", "ev2h_esim_compose", "ev2h_esim_shade",
     "ev2h_pose_track_prepare", "ev2h_pose_track_rows", "ev2h_pose_track_hand_size",
     # test hooks, not part of the stable interface (include/ev2hands_hip.h: "Test hooks"; ev2hands_amd/ops.py: *_rows16, dense_zsum, ...)
     "ev2h_dbg_fp_mlp_rows16", "ev2h_dbg_gemm_zsum_supported", "ev2h_dbg_gemm_zsum", "ev2h_dbg_attn_simfold_partials", "ev2h_dbg_attn_context_rows16",
-    "ev2h_dbg_mano_fit_seq_sweeps",
+    "ev2h_dbg_mano_fit_seq_sweeps", "ev2h_esim_merge_partition_host", "ev2h_dbg_esim_wide_sort",
 ]
 
 _lib = None
@@ -284,6 +286,11 @@ def lib() -> C.CDLL:
     L.ev2h_esim_scratch_bytes.argtypes = [ci, ci, ci, ci, ci]
     L.ev2h_esim_step.argtypes = [vp, ci, ci, ci, vp, ci, vp, vp, C.c_double, C.c_double, C.c_double, C.c_double, ci, ci, ci, vp, vp, vp, vp,
                                  ci, vp, ci, vp, C.c_size_t, vp]
+    L.ev2h_esim_scratch_bytes_wide.restype = C.c_size_t
+    L.ev2h_esim_scratch_bytes_wide.argtypes = L.ev2h_esim_scratch_bytes.argtypes
+    L.ev2h_esim_step_wide.argtypes = L.ev2h_esim_step.argtypes
+    L.ev2h_esim_merge_partition_host.argtypes = [vp, ci, vp, ci, ci]
+    L.ev2h_dbg_esim_wide_sort.argtypes = [ci, ci, ci, ci, vp, ci, vp, C.c_double, ci, vp, ci, vp, C.c_size_t, vp]
     L.ev2h_esim_compose.argtypes = [vp, vp, vp, ci, ci, ci, ci, ci, ci, vp, vp]
     L.ev2h_esim_shade.argtypes = [vp, vp, vp, C.c_size_t, vp, ci, vp, ci, ci, ci, ci] + [C.c_float] * 9 + [vp, ci, ci, C.c_uint64, vp, vp, vp, ci, vp, vp]
     L.ev2h_pose_track_hand_size.restype = C.c_size_t

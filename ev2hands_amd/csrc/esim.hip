@@ -18,6 +18,11 @@
 //      esim_keys_kernel + esim_sort_kernel   (interpolated timestamps) the walk again from the chunk's first memory frame, one 64-bit
 //                         key (t, pixel, k, p) per event; then one workgroup per frame sorts its keys in LDS (lds_sort.hpp) and
 //                         writes the rows in (t_ns, y, x, k) order
+//      esim_keys_kernel + esim_tile_sort_kernel + esim_merge_kernel x passes + esim_wide_rows_kernel   (ev2h_esim_step_wide: frames of
+//                         up to 2^20 events) the same keys; every 8192-key tile of a frame sorted in LDS; neighbouring sorted runs
+//                         merged pass by pass between two key arrays, one 8192-key tile of the output per workgroup (merge path);
+//                         rows written from the array the frame's last pass left its keys in.  The number of launches and their
+//                         grids depend on max_events_per_frame alone.
 // Nothing here synchronises, allocates or reads back.
 #include "common.hpp"
 #include "ev2hands_hip.h"
@@ -32,6 +37,7 @@ constexpr int ES_WAVES = ES_BLOCK / 64;
 constexpr int ES_SCAN_THREADS = 1024;
 constexpr int ES_SORT_THREADS = 1024;
 constexpr int ES_SORT_MAX = 8192;             // keys of one frame in LDS: 64 KiB
+constexpr int ES_SORT_WIDE_MAX = EV2H_ESIM_SORT_WIDE_MAX;   // keys of one frame in global memory, sorted tile by tile and merged
 constexpr int ES_MAX_FRAMES = 4096;
 constexpr int ES_MAX_PIXELS = 1 << 22;        // the pixel field of the sort key
 constexpr int KEY_K_SHIFT = 1, KEY_PIX_SHIFT = 8, KEY_T_SHIFT = 30;
@@ -59,7 +65,8 @@ struct EsimScratch {
 
 size_t align16(size_t v) { return (v + 15) & ~(size_t)15; }
 
-size_t scratch_layout(int F, int HW, int mode, int mepf, void* base, EsimScratch* S) {
+// keys2 (the wide step only): where the second [F][mepf] key array of the merge passes goes, behind everything the narrow layout holds
+size_t scratch_layout(int F, int HW, int mode, int mepf, void* base, EsimScratch* S, bool wide = false, unsigned long long** keys2 = nullptr) {
     const int T = (HW + ES_BLOCK - 1) / ES_BLOCK;
     size_t off = 0;
     char* b = (char*)base;
@@ -76,6 +83,10 @@ size_t scratch_layout(int F, int HW, int mode, int mepf, void* base, EsimScratch
         s.mem0 = (double*)take((size_t)HW * 8);
         s.log0 = (double*)take((size_t)HW * 8);
         s.keys = (unsigned long long*)take((size_t)F * mepf * 8);
+        if (wide) {
+            unsigned long long* k2 = (unsigned long long*)take((size_t)F * mepf * 8);
+            if (keys2) *keys2 = k2;
+        }
     }
     if (S) *S = s;
     return off;
@@ -294,6 +305,26 @@ __global__ __launch_bounds__(ES_BLOCK) void esim_keys_kernel(const uint8_t* __re
     }
 }
 
+// what a frame's rows share, and the row of one sorted key: the one decode of the narrow and the wide sort
+struct EsimFrameRows {
+    long long r0, tbase;
+    double ann;
+};
+
+__device__ __forceinline__ EsimFrameRows frame_rows(const EsimParams& P, const EsimScratch& S, int f) {
+    const long long g = S.chunk[0] + f;
+    return {S.row_base[f], (long long)((double)(g - 1) * P.dt), (double)S.ann[f]};
+}
+
+__device__ __forceinline__ void write_key_row(const int32_t* face_id, const uint8_t* labels, double* rows, const EsimParams& P, const EsimFrameRows& R,
+                                              int f, int i, unsigned long long key) {
+    const int p = (int)((key >> KEY_PIX_SHIFT) & (ES_MAX_PIXELS - 1));
+    const long long t_ns = R.tbase + (long long)(key >> KEY_T_SHIFT);
+    const int y = p / P.W, x = p - y * P.W;
+    if (R.r0 + i < P.capacity)
+        write_row(rows, R.r0 + i, x, y, (double)t_ns, (key & 1ull) ? 1.0 : -1.0, R.ann, event_label(face_id, labels, P.nf, (size_t)f * P.HW + p));
+}
+
 __global__ __launch_bounds__(ES_SORT_THREADS) void esim_sort_kernel(const int32_t* __restrict__ face_id, const uint8_t* __restrict__ labels,
                                                                      double* __restrict__ rows, EsimParams P, EsimScratch S) {
     extern __shared__ unsigned long long lds_keys[];
@@ -304,17 +335,85 @@ __global__ __launch_bounds__(ES_SORT_THREADS) void esim_sort_kernel(const int32_
     for (int i = tid; i < np2; i += ES_SORT_THREADS) lds_keys[i] = i < n ? S.keys[(size_t)f * P.mepf + i] : ~0ull;
     __syncthreads();
     bitonic_sort_keys<ES_SORT_THREADS>(lds_keys, np2, tid);
-    const long long g = S.chunk[0] + f, r0 = S.row_base[f];
-    const long long tbase = (long long)((double)(g - 1) * P.dt);
-    const double ann = (double)S.ann[f];
-    for (int i = tid; i < n; i += ES_SORT_THREADS) {
-        const unsigned long long key = lds_keys[i];
-        const int p = (int)((key >> KEY_PIX_SHIFT) & (ES_MAX_PIXELS - 1));
-        const long long t_ns = tbase + (long long)(key >> KEY_T_SHIFT);
-        const int y = p / P.W, x = p - y * P.W;
-        if (r0 + i < P.capacity)
-            write_row(rows, r0 + i, x, y, (double)t_ns, (key & 1ull) ? 1.0 : -1.0, ann, event_label(face_id, labels, P.nf, (size_t)f * P.HW + p));
+    const EsimFrameRows R = frame_rows(P, S, f);
+    for (int i = tid; i < n; i += ES_SORT_THREADS) write_key_row(face_id, labels, rows, P, R, f, i, lds_keys[i]);
+}
+
+// ---- pass 3, interpolated timestamps, frames of more than one LDS tile (ev2h_esim_step_wide) ---------------------------------------
+// A frame's n = S.total[f] keys stand in tiles of ES_SORT_MAX; tile t holds the positions [t ES_SORT_MAX, min((t + 1) ES_SORT_MAX, n)).
+// Every kernel below has the grid (tiles of max_events_per_frame, F); n is uniform over a workgroup, so a workgroup that has nothing
+// to do returns before its first barrier.  Merge pass j merges neighbouring runs of R = ES_SORT_MAX << j keys from one key array
+// into the other; a frame needs the passes with R < n and takes no part in the later ones, so its sorted keys end in array
+// wide_passes(n) & 1 (0: S.keys).  No workgroup reads what another of the same launch writes.
+__host__ __device__ __forceinline__ int wide_passes(int n) {
+    int j = 0;
+    while (((long long)ES_SORT_MAX << j) < n) ++j;
+    return j;
+}
+
+// Merge path: of the first d keys of the merge of the sorted a[0 .. na) and b[0 .. nb), how many come from a (0 <= d <= na + nb).
+// An a key equal to a b key goes first; the simulator's keys are unique.
+__host__ __device__ __forceinline__ int merge_partition(const unsigned long long* a, int na, const unsigned long long* b, int nb, int d) {
+    int lo = d > nb ? d - nb : 0, hi = d < na ? d : na;
+    while (lo < hi) {
+        const int mid = lo + ((hi - lo) >> 1);                            // lo <= mid < hi <= min(d, na), so 0 <= d - 1 - mid < nb
+        if (a[mid] <= b[d - 1 - mid]) lo = mid + 1;
+        else hi = mid;
     }
+    return lo;
+}
+
+__global__ __launch_bounds__(ES_SORT_THREADS) void esim_tile_sort_kernel(EsimParams P, EsimScratch S) {
+    extern __shared__ unsigned long long lds_keys[];
+    const int tid = threadIdx.x, at = blockIdx.x * ES_SORT_MAX, f = blockIdx.y;
+    const int n = S.total[f];
+    if (n > P.mepf || at >= n) return;
+    const int m = n - at < ES_SORT_MAX ? n - at : ES_SORT_MAX;
+    const int np2 = pow2_at_least(m);
+    unsigned long long* keys = S.keys + (size_t)f * P.mepf + at;
+    for (int i = tid; i < np2; i += ES_SORT_THREADS) lds_keys[i] = i < m ? keys[i] : ~0ull;
+    __syncthreads();
+    bitonic_sort_keys<ES_SORT_THREADS>(lds_keys, np2, tid);
+    for (int i = tid; i < m; i += ES_SORT_THREADS) keys[i] = lds_keys[i];
+}
+
+__global__ __launch_bounds__(ES_SORT_THREADS) void esim_merge_kernel(const unsigned long long* __restrict__ src, unsigned long long* __restrict__ dst,
+                                                                      int run, EsimParams P, EsimScratch S) {
+    extern __shared__ unsigned long long lds_keys[];
+    __shared__ int cut[2];
+    const int tid = threadIdx.x, at = blockIdx.x * ES_SORT_MAX, f = blockIdx.y;
+    const int n = S.total[f];
+    if (n > P.mepf || at >= n || n <= run) return;                        // n <= run: the frame is one sorted run already
+    const int base = at / (2 * run) * (2 * run);                          // the pair of runs this output tile lies in
+    const int na_all = n - base < run ? n - base : run;
+    const int nb_all = n - base - na_all < run ? n - base - na_all : run; // 0: a run without a partner, which the same code copies
+    const unsigned long long* a = src + (size_t)f * P.mepf + base;
+    const unsigned long long* b = a + na_all;
+    const int d0 = at - base;
+    const int d1 = d0 + ES_SORT_MAX < na_all + nb_all ? d0 + ES_SORT_MAX : na_all + nb_all;
+    if (tid < 2) cut[tid] = merge_partition(a, na_all, b, nb_all, tid ? d1 : d0);
+    __syncthreads();
+    const int a0 = cut[0], b0 = d0 - a0, na = cut[1] - a0, m = d1 - d0, nb = m - na;
+    // a's share ascending from the front, b's descending from the back, all-ones keys between them: one bitonic sequence
+    const int np2 = pow2_at_least(m);
+    for (int i = tid; i < np2; i += ES_SORT_THREADS)
+        lds_keys[i] = i < na ? a[a0 + i] : (i >= np2 - nb ? b[b0 + (np2 - 1 - i)] : ~0ull);
+    __syncthreads();
+    bitonic_merge_keys<ES_SORT_THREADS>(lds_keys, np2, tid);
+    unsigned long long* out = dst + (size_t)f * P.mepf + at;
+    for (int i = tid; i < m; i += ES_SORT_THREADS) out[i] = lds_keys[i];
+}
+
+__global__ __launch_bounds__(ES_SORT_THREADS) void esim_wide_rows_kernel(const unsigned long long* __restrict__ keys2, const int32_t* __restrict__ face_id,
+                                                                          const uint8_t* __restrict__ labels, double* __restrict__ rows, EsimParams P,
+                                                                          EsimScratch S) {
+    const int tid = threadIdx.x, at = blockIdx.x * ES_SORT_MAX, f = blockIdx.y;
+    const int n = S.total[f];
+    if (n > P.mepf || at >= n) return;                                    // over the sort capacity: reported by pass 2, no rows
+    const unsigned long long* keys = ((wide_passes(n) & 1) ? keys2 : S.keys) + (size_t)f * P.mepf;
+    const int end = n - at < ES_SORT_MAX ? n : at + ES_SORT_MAX;
+    const EsimFrameRows R = frame_rows(P, S, f);
+    for (int i = at + tid; i < end; i += ES_SORT_THREADS) write_key_row(face_id, labels, rows, P, R, f, i, keys[i]);
 }
 
 // ---- the composed frame ------------------------------------------------------------------------------------------------------------
@@ -333,20 +432,39 @@ __global__ __launch_bounds__(ES_BLOCK) void esim_compose_kernel(const uint8_t* _
     }
 }
 
-}  // namespace
-
-extern "C" size_t ev2h_esim_scratch_bytes(int n_frames, int width, int height, int mode, int max_events_per_frame) {
-    if (n_frames < 1 || n_frames > ES_MAX_FRAMES || width < 1 || height < 1 || (long long)width * height > ES_MAX_PIXELS) return 0;
-    if (mode < EV2H_ESIM_FRAME || mode > EV2H_ESIM_INTERPOLATED) return 0;
-    if (mode == EV2H_ESIM_INTERPOLATED && (max_events_per_frame < 1 || max_events_per_frame > ES_SORT_MAX)) return 0;
-    return scratch_layout(n_frames, width * height, mode, max_events_per_frame, nullptr, nullptr);
+// the wide route's launches behind the keys kernel; `stages`: bit 0 the tile sort, bit 1 the merge passes, bit 2 the rows (the step: all)
+int esim_wide_sort(int stages, const int32_t* face_id, const uint8_t* labels, double* rows, const EsimParams& P, const EsimScratch& S,
+                   unsigned long long* keys2, hipStream_t st) {
+    const dim3 grid((P.mepf + ES_SORT_MAX - 1) / ES_SORT_MAX, P.F);
+    const size_t lds = (size_t)pow2_at_least(P.mepf < ES_SORT_MAX ? P.mepf : ES_SORT_MAX) * sizeof(unsigned long long);
+    if (stages & 1) {
+        esim_tile_sort_kernel<<<grid, ES_SORT_THREADS, lds, st>>>(P, S);
+        EV2H_CHECK_LAUNCH();
+    }
+    const int passes = wide_passes(P.mepf);
+    for (int j = 0; j < passes && (stages & 2); ++j) {
+        esim_merge_kernel<<<grid, ES_SORT_THREADS, lds, st>>>((j & 1) ? keys2 : S.keys, (j & 1) ? S.keys : keys2, ES_SORT_MAX << j, P, S);
+        EV2H_CHECK_LAUNCH();
+    }
+    if (stages & 4) {
+        esim_wide_rows_kernel<<<grid, ES_SORT_THREADS, 0, st>>>(keys2, face_id, labels, rows, P, S);
+        EV2H_CHECK_LAUNCH();
+    }
+    return EV2H_OK;
 }
 
-extern "C" int ev2h_esim_step(const uint8_t* rgb, int n_frames, int width, int height, const int32_t* face_id, int nf, const uint8_t* labels,
-                              const double* log_table, double threshold_pos, double threshold_neg, double eps, double fps, int mode,
-                              int max_per_pixel, int max_events_per_frame, double* mem_frame, double* prev_log, int64_t* state, double* rows,
-                              int capacity, int32_t* annotation_frame, int annotation_capacity, void* scratch, size_t scratch_bytes,
-                              ev2h_stream_t stream) {
+size_t esim_scratch_bytes(int n_frames, int width, int height, int mode, int max_events_per_frame, bool wide) {
+    if (n_frames < 1 || n_frames > ES_MAX_FRAMES || width < 1 || height < 1 || (long long)width * height > ES_MAX_PIXELS) return 0;
+    if (mode < EV2H_ESIM_FRAME || mode > EV2H_ESIM_INTERPOLATED) return 0;
+    if (mode == EV2H_ESIM_INTERPOLATED && (max_events_per_frame < 1 || max_events_per_frame > (wide ? ES_SORT_WIDE_MAX : ES_SORT_MAX))) return 0;
+    return scratch_layout(n_frames, width * height, mode, max_events_per_frame, nullptr, nullptr, wide);
+}
+
+// both steps: the checks, the walk, the scan, and the rows by the narrow (one LDS sort per frame) or the wide (tiles and merges) route
+int esim_step(const uint8_t* rgb, int n_frames, int width, int height, const int32_t* face_id, int nf, const uint8_t* labels,
+              const double* log_table, double threshold_pos, double threshold_neg, double eps, double fps, int mode, int max_per_pixel,
+              int max_events_per_frame, double* mem_frame, double* prev_log, int64_t* state, double* rows, int capacity,
+              int32_t* annotation_frame, int annotation_capacity, void* scratch, size_t scratch_bytes, ev2h_stream_t stream, bool wide) {
     EV2H_CHECK_ARG(rgb && log_table && mem_frame && prev_log && state && rows && annotation_frame && scratch);
     EV2H_CHECK_ARG(n_frames >= 1 && n_frames <= ES_MAX_FRAMES && width >= 1 && height >= 1 && (long long)width * height <= ES_MAX_PIXELS);
     EV2H_CHECK_ARG(!(face_id && labels) && (!face_id || nf >= 1));
@@ -356,13 +474,16 @@ extern "C" int ev2h_esim_step(const uint8_t* rgb, int n_frames, int width, int h
     EV2H_CHECK_ARG(mode == EV2H_ESIM_FRAME || (isfinite(fps) && fps > 0.0));
     EV2H_CHECK_ARG(mode != EV2H_ESIM_INTERPOLATED || 1e9 / fps <= 8589934592.0);       // 2^33: a frame's time span fits the key's 34 bits
     EV2H_CHECK_ARG(max_per_pixel >= 1 && max_per_pixel <= 127);
-    EV2H_CHECK_ARG(mode != EV2H_ESIM_INTERPOLATED || (max_events_per_frame >= 1 && max_events_per_frame <= ES_SORT_MAX));
+    EV2H_CHECK_ARG(mode != EV2H_ESIM_INTERPOLATED || (max_events_per_frame >= 1 && max_events_per_frame <= (wide ? ES_SORT_WIDE_MAX : ES_SORT_MAX)));
     EV2H_CHECK_ARG(capacity >= 1 && annotation_capacity >= 1);
     const int HW = width * height;
     EV2H_CHECK_ARG((long long)n_frames * HW * max_per_pixel < 2147483648ll);           // a chunk's row offsets are 32-bit
     EV2H_CHECK_ARG(((uintptr_t)scratch & 15) == 0);
+    // both key arrays' byte offsets, and the layout's sum over them, stay inside size_t (always so where size_t has 64 bits)
+    EV2H_CHECK_ARG(mode != EV2H_ESIM_INTERPOLATED || (unsigned long long)n_frames * (unsigned long long)max_events_per_frame <= SIZE_MAX / 64);
     EsimScratch S;
-    EV2H_CHECK_ARG(scratch_bytes >= scratch_layout(n_frames, HW, mode, max_events_per_frame, scratch, &S));
+    unsigned long long* keys2 = nullptr;
+    EV2H_CHECK_ARG(scratch_bytes >= scratch_layout(n_frames, HW, mode, max_events_per_frame, scratch, &S, wide, &keys2));
     EsimParams P;
     P.tp = threshold_pos, P.tn = threshold_neg, P.eps = eps, P.fps = fps, P.dt = mode == EV2H_ESIM_FRAME ? 0.0 : 1e9 / fps;
     P.mode = mode, P.max_pp = max_per_pixel, P.mepf = max_events_per_frame, P.nf = nf;
@@ -380,11 +501,50 @@ extern "C" int ev2h_esim_step(const uint8_t* rgb, int n_frames, int width, int h
     } else {
         esim_keys_kernel<<<P.T, ES_BLOCK, 0, st>>>(rgb, log_table, P, S);
         EV2H_CHECK_LAUNCH();
-        const size_t lds = (size_t)pow2_at_least(max_events_per_frame) * sizeof(unsigned long long);
-        esim_sort_kernel<<<n_frames, ES_SORT_THREADS, lds, st>>>(face_id, labels, rows, P, S);
-        EV2H_CHECK_LAUNCH();
+        if (!wide) {
+            const size_t lds = (size_t)pow2_at_least(max_events_per_frame) * sizeof(unsigned long long);
+            esim_sort_kernel<<<n_frames, ES_SORT_THREADS, lds, st>>>(face_id, labels, rows, P, S);
+            EV2H_CHECK_LAUNCH();
+        } else {
+            return esim_wide_sort(7, face_id, labels, rows, P, S, keys2, st);
+        }
     }
     return EV2H_OK;
+}
+
+}  // namespace
+
+extern "C" size_t ev2h_esim_scratch_bytes(int n_frames, int width, int height, int mode, int max_events_per_frame) {
+    return esim_scratch_bytes(n_frames, width, height, mode, max_events_per_frame, false);
+}
+
+extern "C" size_t ev2h_esim_scratch_bytes_wide(int n_frames, int width, int height, int mode, int max_events_per_frame) {
+    return esim_scratch_bytes(n_frames, width, height, mode, max_events_per_frame, true);
+}
+
+extern "C" int ev2h_esim_step(const uint8_t* rgb, int n_frames, int width, int height, const int32_t* face_id, int nf, const uint8_t* labels,
+                              const double* log_table, double threshold_pos, double threshold_neg, double eps, double fps, int mode,
+                              int max_per_pixel, int max_events_per_frame, double* mem_frame, double* prev_log, int64_t* state, double* rows,
+                              int capacity, int32_t* annotation_frame, int annotation_capacity, void* scratch, size_t scratch_bytes,
+                              ev2h_stream_t stream) {
+    return esim_step(rgb, n_frames, width, height, face_id, nf, labels, log_table, threshold_pos, threshold_neg, eps, fps, mode, max_per_pixel,
+                     max_events_per_frame, mem_frame, prev_log, state, rows, capacity, annotation_frame, annotation_capacity, scratch, scratch_bytes,
+                     stream, false);
+}
+
+extern "C" int ev2h_esim_step_wide(const uint8_t* rgb, int n_frames, int width, int height, const int32_t* face_id, int nf, const uint8_t* labels,
+                                   const double* log_table, double threshold_pos, double threshold_neg, double eps, double fps, int mode,
+                                   int max_per_pixel, int max_events_per_frame, double* mem_frame, double* prev_log, int64_t* state, double* rows,
+                                   int capacity, int32_t* annotation_frame, int annotation_capacity, void* scratch, size_t scratch_bytes,
+                                   ev2h_stream_t stream) {
+    return esim_step(rgb, n_frames, width, height, face_id, nf, labels, log_table, threshold_pos, threshold_neg, eps, fps, mode, max_per_pixel,
+                     max_events_per_frame, mem_frame, prev_log, state, rows, capacity, annotation_frame, annotation_capacity, scratch, scratch_bytes,
+                     stream, true);
+}
+
+extern "C" int ev2h_esim_merge_partition_host(const uint64_t* a, int na, const uint64_t* b, int nb, int d) {
+    if (na < 0 || nb < 0 || d < 0 || (long long)d > (long long)na + nb || (na && !a) || (nb && !b)) return -1;
+    return merge_partition(reinterpret_cast<const unsigned long long*>(a), na, reinterpret_cast<const unsigned long long*>(b), nb, d);
 }
 
 extern "C" int ev2h_esim_compose(const uint8_t* frame, const int32_t* face_id, const uint8_t* background, int n_frames, int width, int height,
@@ -399,4 +559,20 @@ extern "C" int ev2h_esim_compose(const uint8_t* frame, const int32_t* face_id, c
                                                                       (float)blue, rgb);
     EV2H_CHECK_LAUNCH();
     return EV2H_OK;
+}
+
+extern "C" int ev2h_dbg_esim_wide_sort(int stages, int n_frames, int width, int height, const int32_t* face_id, int nf, const uint8_t* labels,
+                                       double fps, int max_events_per_frame, double* rows, int capacity, void* scratch, size_t scratch_bytes,
+                                       ev2h_stream_t stream) {
+    EV2H_CHECK_ARG(stages >= 1 && stages <= 7 && rows && scratch && ((uintptr_t)scratch & 15) == 0 && capacity >= 1);
+    EV2H_CHECK_ARG(n_frames >= 1 && n_frames <= ES_MAX_FRAMES && width >= 1 && height >= 1 && (long long)width * height <= ES_MAX_PIXELS);
+    EV2H_CHECK_ARG(!(face_id && labels) && (!face_id || nf >= 1) && isfinite(fps) && fps > 0.0 && 1e9 / fps <= 8589934592.0);
+    EV2H_CHECK_ARG(max_events_per_frame >= 1 && max_events_per_frame <= ES_SORT_WIDE_MAX);
+    EsimScratch S;
+    unsigned long long* keys2 = nullptr;
+    EV2H_CHECK_ARG(scratch_bytes >= scratch_layout(n_frames, width * height, EV2H_ESIM_INTERPOLATED, max_events_per_frame, scratch, &S, true, &keys2));
+    EsimParams P = {};
+    P.fps = fps, P.dt = 1e9 / fps, P.mode = EV2H_ESIM_INTERPOLATED, P.mepf = max_events_per_frame, P.nf = nf;
+    P.W = width, P.H = height, P.HW = width * height, P.T = (P.HW + ES_BLOCK - 1) / ES_BLOCK, P.F = n_frames, P.capacity = capacity;
+    return esim_wide_sort(stages, face_id, labels, rows, P, S, keys2, (hipStream_t)stream);
 }

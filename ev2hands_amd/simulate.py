@@ -61,8 +61,11 @@ class EventSimulatorS:
     """hands: {'left', 'right'} of ManoHand (net.hands).  threshold_pos / threshold_neg / eps: the contrast thresholds (the reference:
     0.4, 0.4, 1e-6; both thresholds must exceed 2 eps).  timestamps: "frame" | "scaled" | "interpolated" (module docstring).
     capacity: rows of the table; max_annotations: entries of annotation_frame; chunk: the most frames one step takes;
-    max_per_pixel (<= 127): the bound of a pixel's events in one frame; max_events_per_frame (<= 8192): the interpolated order's
-    sort capacity.  background: uint8 [H, W, 3] (default all 159); hand_color: RGB.  f, cx, cy: the camera (DemoFrames' defaults).
+    max_per_pixel (<= 127): the bound of a pixel's events in one frame; max_events_per_frame (1 .. 2**20, default 8192): the interpolated order's
+    sort capacity -- up to 8192 a frame is sorted in one workgroup's LDS (ev2h_esim_step); above that its 8192-key tiles are sorted and
+    merged through two key arrays in the scratch of `begin` (ev2h_esim_step_wide), 2 * 8 * chunk * max_events_per_frame bytes (33.5 MB at
+    chunk = 64 and 32768; a full-sensor frame under the reference lights holds 12 300 events on average).
+    background: uint8 [H, W, 3] (default all 159); hand_color: RGB.  f, cx, cy: the camera (DemoFrames' defaults).
     appearance: an appearance.HandAppearance -- `render` / `step` / `step_track` then shade the frames with it (hand_color is not used);
     None: the flat colouring."""
 
@@ -81,9 +84,9 @@ class EventSimulatorS:
         self.max_pp, self.mepf, self.max_annotations = int(max_per_pixel), int(max_events_per_frame), int(max_annotations)
         if not (self.tp > 2 * self.eps and self.tn > 2 * self.eps and self.eps >= 0):
             raise ValueError("threshold_pos > 2 eps, threshold_neg > 2 eps and eps >= 0 required (else both loops could run for one pixel)")
-        if not (self.fps > 0 and 1 <= self.capacity < 2 ** 31 and 1 <= self.chunk <= 4096 and 1 <= self.max_pp <= 127 and 1 <= self.mepf <= 8192
+        if not (self.fps > 0 and 1 <= self.capacity < 2 ** 31 and 1 <= self.chunk <= 4096 and 1 <= self.max_pp <= 127 and 1 <= self.mepf <= _lib.ESIM_SORT_WIDE_MAX
                 and self.max_annotations >= 1 and self.w >= 1 and self.h >= 1):
-            raise ValueError("fps > 0, 1 <= capacity < 2**31, 1 <= chunk <= 4096, 1 <= max_per_pixel <= 127, 1 <= max_events_per_frame <= 8192 required")
+            raise ValueError("fps > 0, 1 <= capacity < 2**31, 1 <= chunk <= 4096, 1 <= max_per_pixel <= 127, 1 <= max_events_per_frame <= 2**20 required")
         self.hand_color = tuple(int(c) for c in hand_color)
         if len(self.hand_color) != 3 or not all(0 <= c <= 255 for c in self.hand_color):
             raise ValueError("hand_color must be three bytes (R, G, B)")
@@ -104,7 +107,11 @@ class EventSimulatorS:
             if not isinstance(appearance, HandAppearance) or appearance.device != self.device or appearance.nv != self.frames.nv:
                 raise ValueError(f"appearance must be a HandAppearance on {self.device} with {self.frames.nv} colours per hand")
         self.table = torch.from_numpy(log_table()).to(self.device)
-        self.scratch_bytes = int(_lib.lib().ev2h_esim_scratch_bytes(self.chunk, self.w, self.h, self.mode, self.mepf))
+        wide = self.mepf > _lib.ESIM_SORT_MAX                                   # up to 8192: the export and the scratch as they were
+        self._step_name = "ev2h_esim_step_wide" if wide else "ev2h_esim_step"
+        self._step_fn = getattr(_lib.lib(), self._step_name)
+        size_fn = _lib.lib().ev2h_esim_scratch_bytes_wide if wide else _lib.lib().ev2h_esim_scratch_bytes
+        self.scratch_bytes = int(size_fn(self.chunk, self.w, self.h, self.mode, self.mepf))
         if self.scratch_bytes == 0:
             raise ValueError("chunk, width, height or max_events_per_frame out of range (include/ev2hands_hip.h: ev2h_esim_step)")
         self.rows = None
@@ -164,11 +171,11 @@ class EventSimulatorS:
                 raise ValueError("labels from face_id need the hands' faces (hands=None): give a label map")
         if labels is not None:
             _dev_tensor(labels, "labels", torch.uint8, (F, self.h, self.w), self.device)
-        _lib.check(_lib.lib().ev2h_esim_step(rgb.data_ptr(), F, self.w, self.h, _lib.ptr(face_id), nf, _lib.ptr(labels), self.table.data_ptr(),
-                                             self.tp, self.tn, self.eps, self.fps, self.mode, self.max_pp, self.mepf, self.mem_frame.data_ptr(),
-                                             self.prev_log.data_ptr(), self.state.data_ptr(), self.rows.data_ptr(), self.capacity,
-                                             self.annotation_frame.data_ptr(), self.max_annotations, self._scratch.data_ptr(),
-                                             self._scratch.numel(), _lib.stream_handle()), "ev2h_esim_step")
+        _lib.check(self._step_fn(rgb.data_ptr(), F, self.w, self.h, _lib.ptr(face_id), nf, _lib.ptr(labels), self.table.data_ptr(),
+                                 self.tp, self.tn, self.eps, self.fps, self.mode, self.max_pp, self.mepf, self.mem_frame.data_ptr(),
+                                 self.prev_log.data_ptr(), self.state.data_ptr(), self.rows.data_ptr(), self.capacity,
+                                 self.annotation_frame.data_ptr(), self.max_annotations, self._scratch.data_ptr(),
+                                 self._scratch.numel(), _lib.stream_handle()), self._step_name)
         self.n_frames += F
 
     def render(self, params_left, params_right, present=None, lights=None):
@@ -245,7 +252,7 @@ class EventSimulatorS:
         s = info["status"]
         if s & _lib.ESIM_OVER_SORT:
             raise RuntimeError(f"frame {info['sort_frame']} holds {info['sort_count']} events, more than max_events_per_frame = {self.mepf}: "
-                               "its rows were not written (there is no fallback order)")
+                               f"its rows were not written (there is no fallback order; max_events_per_frame can be raised up to {_lib.ESIM_SORT_WIDE_MAX})")
         if s & _lib.ESIM_LOOP_BOUND:
             raise RuntimeError(f"a pixel reached max_per_pixel = {self.max_pp} events in one frame")
         if s & _lib.ESIM_OVER_CAPACITY:

@@ -955,7 +955,7 @@ int ev2h_render_hands(const float* verts_left, const float* verts_right, size_t 
  *   esim_torch unpinned.  Event k = 1 .. n of a pixel in frame f, with mem the memory value before the frame, L0 the previous
  *   frame's log value and L1 this one's:  level = mem + k tp (mem - k tn),  frac = (level - L0) / (L1 - L0) clamped to [0, 1] (a
  *   NaN counts as 0),  t_ns = (int64)(((f - 1) + frac) * (1e9 / fps)), truncated; a frame's rows are ordered by (t_ns, y, x, k).
- *   A frame with more than max_events_per_frame (1 .. 8192) events sets EV2H_ESIM_OVER_SORT and gets NO rows: its rows are counted
+ *   A frame with more than max_events_per_frame (1 .. 8192; ev2h_esim_step_wide below: 1 .. 2^20) events sets EV2H_ESIM_OVER_SORT and gets NO rows: its rows are counted
  *   and the rows of later frames keep their offsets, so the table then holds a gap of that many rows that nothing wrote -- a table
  *   with this bit set is not to be used (EventSimulatorS.finish raises).  1e9 / fps <= 2^33.
  *
@@ -983,6 +983,29 @@ int ev2h_esim_step(const uint8_t* rgb, int n_frames, int width, int height, cons
                    int max_per_pixel, int max_events_per_frame, double* mem_frame, double* prev_log, int64_t* state, double* rows,
                    int capacity, int32_t* annotation_frame, int annotation_capacity, void* scratch, size_t scratch_bytes,
                    ev2h_stream_t stream);
+/* ev2h_esim_step for frames of more than 8192 events under EV2H_ESIM_INTERPOLATED: the same arguments, state, rule, rows, status
+ * bits and checks, with max_events_per_frame in 1 .. EV2H_ESIM_SORT_WIDE_MAX (2^20); the other modes do what ev2h_esim_step does.
+ * The walk, the scan and the keys are ev2h_esim_step's own kernels.  A frame's keys are then sorted in tiles of 8192 in LDS and
+ * neighbouring sorted runs are merged in ceil(log2(ceil(max_events_per_frame / 8192))) passes between two key arrays, each
+ * workgroup producing one 8192-key tile of the output from the two merge-path diagonals it finds by binary search; a frame that
+ * needs fewer passes sits out the later ones.  The comparisons are on the whole 64-bit key (t_ns, pixel, k), and keys are unique:
+ * a frame's rows are in (t_ns, y, x, k) order, the bytes ev2h_esim_step writes for a frame it can hold.  The number of launches and
+ * their grids depend on max_events_per_frame alone, nothing is read back, there are no atomics: the same call gives the same bytes
+ * and any split of a sequence into calls gives the same bytes.  A frame with more than max_events_per_frame events keeps
+ * ev2h_esim_step's contract: EV2H_ESIM_OVER_SORT, the first such frame and its count in the state, no rows, later frames at their
+ * offsets.
+ * scratch: ev2h_esim_scratch_bytes_wide(...) bytes (0: arguments out of range) -- ev2h_esim_scratch_bytes' layout with a second
+ * [n_frames][max_events_per_frame] array of 64-bit keys, so under EV2H_ESIM_INTERPOLATED the two key arrays take
+ * 2 * 8 * n_frames * max_events_per_frame bytes (33.5 MB at 64 frames of 32768).  EV2H_ERR_ARG before any launch: everything
+ * ev2h_esim_step lists, max_events_per_frame outside 1 .. 2^20, a scratch smaller than the wide layout, n_frames *
+ * max_events_per_frame too large for the key arrays' byte offsets in size_t. */
+#define EV2H_ESIM_SORT_WIDE_MAX 1048576
+size_t ev2h_esim_scratch_bytes_wide(int n_frames, int width, int height, int mode, int max_events_per_frame);
+int ev2h_esim_step_wide(const uint8_t* rgb, int n_frames, int width, int height, const int32_t* face_id, int nf, const uint8_t* labels,
+                        const double* log_table, double threshold_pos, double threshold_neg, double eps, double fps, int mode,
+                        int max_per_pixel, int max_events_per_frame, double* mem_frame, double* prev_log, int64_t* state, double* rows,
+                        int capacity, int32_t* annotation_frame, int annotation_capacity, void* scratch, size_t scratch_bytes,
+                        ev2h_stream_t stream);
 /* The frame the simulator sees for a rendered chunk: frame [n_frames][height][width][3] uint8 as ev2h_render_hands writes it (its
  * intensity I is byte 2) and face_id; a pixel with face_id >= 0 gets (uint8)(int)((float)I / 255.0f * colour + 0.5f) per channel
  * (float32, one rounding per operation), every other pixel background [height][width][3].  rgb [n_frames][height][width][3].
@@ -1333,6 +1356,16 @@ int ev2h_dbg_mano_fit_seq_sweeps(const ev2h_mano_consts* c, const float* params0
                                  size_t targets_stride, const float* weights, size_t weights_stride, const ev2h_mano_fit_seq_opts* opts,
                                  void* workspace, size_t workspace_bytes, double* out_rows, double* per_frame_cost, double* stats,
                                  int32_t* info, ev2h_stream_t stream, int n_sweeps);
+/* ev2h_esim_merge_partition_host, csrc/esim.hip: the merge-path search of ev2h_esim_step_wide's merge passes, run on the host on host
+ * arrays (the search is one __host__ __device__ function).  a [na] and b [nb] sorted ascending, 0 <= d <= na + nb: -> how many of the
+ * first d keys of their merge come from a (an a key equal to a b key goes first); -1: a bad argument.  No device is touched. */
+int ev2h_esim_merge_partition_host(const uint64_t* a, int na, const uint64_t* b, int nb, int d);
+/* ev2h_dbg_esim_wide_sort, csrc/esim.hip: the launches of ev2h_esim_step_wide behind its keys kernel, on the scratch a call of it with the
+ * same n_frames, width, height and max_events_per_frame left behind -- stages bit 0: the tile sort, bit 1: the merge passes, bit 2: the
+ * row writer.  Run again on that scratch they do the work of the step's own (on keys that are sorted already; the network and the
+ * merge do not depend on it) and write the same rows.  For tools/esim_wide_timing.py, which times each by device events. */
+int ev2h_dbg_esim_wide_sort(int stages, int n_frames, int width, int height, const int32_t* face_id, int nf, const uint8_t* labels, double fps,
+                            int max_events_per_frame, double* rows, int capacity, void* scratch, size_t scratch_bytes, ev2h_stream_t stream);
 
 #ifdef __cplusplus
 }
