@@ -164,11 +164,12 @@ EXPORTS = [
     "ev2h_mano_backward", "ev2h_segmentation_score_backward", "ev2h_loss_terms_backward", "ev2h_collision_penalty_backward",
     "ev2h_mano_joints_jacobian", "ev2h_mano_fit", "ev2h_mano_fit_opts_size",
     "ev2h_mano_fit_seq", "ev2h_mano_fit_seq_opts_size", "ev2h_mano_fit_seq_workspace_bytes",
+    "ev2h_mano_fit_seq_segments", "ev2h_mano_fit_seq_segments_workspace_bytes",
     "ev2h_esim_scratch_bytes", "ev2h_esim_step", "ev2h_esim_scratch_bytes_wide", "ev2h_esim_step_wide", "ev2h_esim_compose", "ev2h_esim_shade",
     "ev2h_pose_track_prepare", "ev2h_pose_track_rows", "ev2h_pose_track_hand_size",
     # test hooks, not part of the stable interface (include/ev2hands_hip.h: "Test hooks"; ev2hands_amd/ops.py: *_rows16, dense_zsum, ...)
     "ev2h_dbg_fp_mlp_rows16", "ev2h_dbg_gemm_zsum_supported", "ev2h_dbg_gemm_zsum", "ev2h_dbg_attn_simfold_partials", "ev2h_dbg_attn_context_rows16",
-    "ev2h_dbg_mano_fit_seq_sweeps", "ev2h_esim_merge_partition_host", "ev2h_dbg_esim_wide_sort",
+    "ev2h_dbg_mano_fit_seq_sweeps", "ev2h_dbg_mano_fit_seq_segments_solves", "ev2h_esim_merge_partition_host", "ev2h_dbg_esim_wide_sort",
 ]
 
 _lib = None
@@ -278,6 +279,10 @@ def lib() -> C.CDLL:
     L.ev2h_mano_fit_seq.argtypes = [C.POINTER(ManoConsts), vp, ci, vp, ci, vp, C.c_size_t, vp, C.c_size_t, C.POINTER(ManoFitSeqOpts), vp, C.c_size_t,
                                     vp, vp, vp, vp, vp]
     L.ev2h_dbg_mano_fit_seq_sweeps.argtypes = L.ev2h_mano_fit_seq.argtypes + [ci]
+    L.ev2h_mano_fit_seq_segments.argtypes = L.ev2h_mano_fit_seq.argtypes + [ci]
+    L.ev2h_dbg_mano_fit_seq_segments_solves.argtypes = L.ev2h_mano_fit_seq.argtypes + [ci, ci]
+    L.ev2h_mano_fit_seq_segments_workspace_bytes.restype = C.c_size_t
+    L.ev2h_mano_fit_seq_segments_workspace_bytes.argtypes = [ci, ci, ci, ci, ci]
     L.ev2h_mano_fit_seq_opts_size.restype = C.c_size_t
     L.ev2h_mano_fit_seq_opts_size.argtypes = []
     L.ev2h_mano_fit_seq_workspace_bytes.restype = C.c_size_t

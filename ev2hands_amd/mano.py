@@ -9,6 +9,8 @@ in metres.  The arithmetic runs in the HIP kernel `ev2h_mano` (csrc/mano.hip).
 from __future__ import annotations
 
 import ctypes as C
+import math
+import numbers
 import os
 import pickle
 
@@ -16,6 +18,15 @@ import numpy as np
 import torch
 
 from . import _lib, synth
+
+
+
+
+def default_segment(longest: int) -> int:
+    """ManoHand.fit_sequence(solver="segments", segment=None): floor(sqrt(the longest sequence's frames)).  A frame of a segment and a
+    separator cost about the same (60 and 56 microseconds at n_pose 6), the segments run abreast and the separators one after the
+    other, so a solve takes about segment * a + F / segment * b: least near sqrt(F) (DESIGN.md 6.14 has the measurement)."""
+    return max(1, math.isqrt(int(longest)))
 
 
 PACKED_NAMES = ("hands_mean", "comps", "blend_T", "v_template", "J_template", "J_shape", "weights")
@@ -234,7 +245,7 @@ class ManoHand:
 
     def fit_sequence(self, j3d, offsets=None, weights=None, init="frames", smooth=(0.0, 0.0, 0.0, 0.0), share_betas: bool = True,
                      lam_pose: float = 0.0, lam_shape: float = 0.0, free=_lib.FIT_GROUPS, max_iters: int = 32, mu0: float = 1e-3,
-                     ftol: float = 1e-12, _sweeps_only=None):
+                     ftol: float = 1e-12, solver: str = "sweep", segment=None, _sweeps_only=None):
         """ev2h_mano_fit_seq: fit whole sequences of one hand, one least-squares problem per sequence with first-difference
         smoothness between neighbouring frames and (share_betas) one betas vector (include/ev2hands_hip.h states the problem and the
         Levenberg-Marquardt rules).  j3d float32 [F, 21, 3] in metres and weights [F, 21] as `fit` takes them; a frame without any
@@ -244,7 +255,23 @@ class ManoHand:
         "frames": `fit(init="rigid")` of every frame with the same priors and `free`, a frame without data taking the row of the
         nearest earlier frame of its sequence that has data (the nearest later one in a leading gap), and with share_betas every
         row's betas set to the mean over the sequence's frames that have data (`sequence_start_rows`).  -> ManoSequenceFit.
-        No host synchronisation.  (_sweeps_only = n: the test hook ev2h_dbg_mano_fit_seq_sweeps instead, for tools/mano_fit_seq_timing.py.)"""
+        solver: "sweep" (one wavefront walks a sequence's frames; `segment` must be None) or "segments"
+        (ev2h_mano_fit_seq_segments: every `segment` + 1-th frame is a separator, the segments between them are eliminated abreast,
+        the separators by one wavefront; the same equations in another elimination order, so equal up to rounding and not bit for
+        bit).  segment: an int >= 1, None = default_segment(the longest sequence's frames), its square root.
+        No host synchronisation.  (_sweeps_only = n: the test hooks ev2h_dbg_mano_fit_seq_sweeps / ..._segments_solves instead, for
+        tools/mano_fit_seq_timing.py and tools/mano_fit_seq_segments_timing.py.)"""
+        if solver not in ("sweep", "segments"):
+            raise ValueError(f'solver is "sweep" or "segments", got {solver!r}')
+        if solver == "sweep":
+            if segment is not None:
+                raise ValueError('segment belongs to solver="segments"')
+        elif segment is None:
+            pass
+        elif isinstance(segment, bool) or not isinstance(segment, numbers.Integral) or segment < 1:
+            raise ValueError(f"segment must be an int >= 1, got {segment!r}")
+        else:
+            segment = min(int(segment), 2 ** 31 - 1)
         P, K = 16 + self.ncomps, self.ncomps
         if not isinstance(j3d, torch.Tensor) or j3d.dim() != 3 or j3d.shape[0] < 1:
             raise ValueError("j3d must be a float32 [F, 21, 3] CUDA tensor with F >= 1")
@@ -289,7 +316,12 @@ class ManoHand:
         opts = _lib.ManoFitSeqOpts(float(lam_pose), float(lam_shape), (C.c_double * 4)(*smooth), float(mu0), float(ftol), int(max_iters),
                                    sum(1 << i for i, g in enumerate(_lib.FIT_GROUPS) if g in free), 1 if share_betas else 0)
         L = _lib.lib()
-        nbytes = int(L.ev2h_mano_fit_seq_workspace_bytes(K, F, S, opts.share_betas))
+        if solver == "segments" and segment is None:
+            segment = default_segment(max(b - a for a, b in zip(offsets, offsets[1:])))
+        if solver == "sweep":
+            nbytes = int(L.ev2h_mano_fit_seq_workspace_bytes(K, F, S, opts.share_betas))
+        else:
+            nbytes = int(L.ev2h_mano_fit_seq_segments_workspace_bytes(K, F, S, opts.share_betas, segment))
         if nbytes == 0:
             raise ValueError("ev2h_mano_fit_seq_workspace_bytes refused the sizes")
         ws = torch.empty(nbytes // 8, device=self.device, dtype=torch.float64)
@@ -302,7 +334,12 @@ class ManoHand:
         args = (C.byref(c), init.data_ptr(), int(init.stride(0)) if F > 1 else P, off, S, j3d.data_ptr(), int(j3d.stride(0)) if F > 1 else 0,
                 _lib.ptr(weights), int(weights.stride(0)) if weights is not None and F > 1 else 0, C.byref(opts), ws.data_ptr(), nbytes,
                 out.data_ptr(), frame_cost.data_ptr(), stats.data_ptr(), info.data_ptr(), _lib.stream_handle())
-        if _sweeps_only is None:
+        if solver == "segments":
+            if _sweeps_only is None:
+                _lib.check(L.ev2h_mano_fit_seq_segments(*args, segment), "ev2h_mano_fit_seq_segments")
+            else:
+                _lib.check(L.ev2h_dbg_mano_fit_seq_segments_solves(*args, segment, int(_sweeps_only)), "ev2h_dbg_mano_fit_seq_segments_solves")
+        elif _sweeps_only is None:
             _lib.check(L.ev2h_mano_fit_seq(*args), "ev2h_mano_fit_seq")
         else:
             _lib.check(L.ev2h_dbg_mano_fit_seq_sweeps(*args, int(_sweeps_only)), "ev2h_dbg_mano_fit_seq_sweeps")

@@ -474,6 +474,32 @@ int ev2h_mano_fit_seq(const ev2h_mano_consts* c, const float* params0, int ldp, 
                       size_t targets_stride, const float* weights, size_t weights_stride, const ev2h_mano_fit_seq_opts* opts,
                       void* workspace, size_t workspace_bytes, double* out_rows, double* per_frame_cost, double* stats, int32_t* info,
                       ev2h_stream_t stream);
+/* ev2h_mano_fit_seq with another elimination order (csrc/mano_fit_seq.hip): the same problem, the same normal equations, the same
+ * Levenberg-Marquardt rules, inputs, outputs and statuses; the sweep down all frames of a sequence, one wavefront per sequence, is
+ * replaced by one level of nested dissection over the frames.  With q = segment + 1, frame k of a sequence (k counted from its first
+ * frame) is a SEPARATOR where k % q == segment; the runs of at most `segment` frames between separators are SEGMENTS (F <= segment: one
+ * segment and no separator; the last segment may be shorter, and is missing where F % q == 0).  The unknowns are ordered
+ * [segment interiors | separators | shared betas]:
+ *   H + mu D is block-diagonal over the segments, each block-tridiagonal as before; a segment's first frame is coupled to the separator
+ *     on its left and its last frame to the separator on its right by -diag(smooth); a frame's diagonal carries +smooth once per
+ *     neighbour it has in the sequence, separator or not, and then mu D as before.
+ *   Eliminating the segments (all segments of all sequences abreast) leaves a block-tridiagonal system over the separators with DENSE
+ *     off-diagonal blocks and the 10-column border, which one wavefront per sequence factors and solves; the segments are then
+ *     back-substituted abreast.  A pivot that is not finite or not positive anywhere -- a segment, a separator, the border -- is a
+ *     rejected step.
+ * The host issues 2 + 6 * max_iters launches (linearise, segments down, separators, segments up, trial cost, decide) and reads nothing.
+ * No atomics; every sum runs in an order fixed by (F_s, segment): the same call gives the same bytes and a sequence's outputs depend on
+ * its own inputs, opts and `segment` alone.  The result is NOT ev2h_mano_fit_seq's bit for bit, nor another segment's: it is another
+ * elimination order of the same equations (equal up to rounding).  A frozen group's rows come back bit for bit.
+ * workspace: at least ev2h_mano_fit_seq_segments_workspace_bytes(K, n_frames, S, share_betas, segment) bytes (0 for sizes it refuses):
+ * ev2h_mano_fit_seq's plus n^2 doubles per frame (the coupling columns; n = 6 + K shared, else 16 + K) and, per segment, two packed
+ * and two full n x n blocks, n x ncol sums and the border's partial sums.  A segment longer than n_frames counts as n_frames.
+ * EV2H_ERR_ARG before any launch: what ev2h_mano_fit_seq refuses, segment < 1, a workspace too small for this segment. */
+size_t ev2h_mano_fit_seq_segments_workspace_bytes(int K, int n_frames, int S, int share_betas, int segment);
+int ev2h_mano_fit_seq_segments(const ev2h_mano_consts* c, const float* params0, int ldp, const int32_t* offsets, int S, const float* targets,
+                               size_t targets_stride, const float* weights, size_t weights_stride, const ev2h_mano_fit_seq_opts* opts,
+                               void* workspace, size_t workspace_bytes, double* out_rows, double* per_frame_cost, double* stats,
+                               int32_t* info, ev2h_stream_t stream, int segment);
 
 /* ---- event window -> [5, N] tensor (next row 8f-1; dataset/evaluation_stream.py:187-225, ev2hands_r.py:108-159, erpc.py:169-249) ---- */
 /* Per-pixel accumulation + np.nonzero-order compaction of B ragged windows.  events: device float64 rows of ev_stride (>= 4)
@@ -1356,6 +1382,14 @@ int ev2h_dbg_mano_fit_seq_sweeps(const ev2h_mano_consts* c, const float* params0
                                  size_t targets_stride, const float* weights, size_t weights_stride, const ev2h_mano_fit_seq_opts* opts,
                                  void* workspace, size_t workspace_bytes, double* out_rows, double* per_frame_cost, double* stats,
                                  int32_t* info, ev2h_stream_t stream, int n_sweeps);
+/* ev2h_dbg_mano_fit_seq_segments_solves, csrc/mano_fit_seq.hip: the same for ev2h_mano_fit_seq_segments -- ONE linearisation, then
+ * (n & 0xff) (0..64) solves of the segmented solver on it.  n >> 8, where not 0, picks which of a solve's three kernels are launched:
+ * bit 0 segments down, bit 1 separators, bit 2 segments up (a kernel run alone finds what an earlier full solve on the same workspace
+ * left).  For tools/mano_fit_seq_segments_timing.py. */
+int ev2h_dbg_mano_fit_seq_segments_solves(const ev2h_mano_consts* c, const float* params0, int ldp, const int32_t* offsets, int S,
+                                          const float* targets, size_t targets_stride, const float* weights, size_t weights_stride,
+                                          const ev2h_mano_fit_seq_opts* opts, void* workspace, size_t workspace_bytes, double* out_rows,
+                                          double* per_frame_cost, double* stats, int32_t* info, ev2h_stream_t stream, int segment, int n);
 /* ev2h_esim_merge_partition_host, csrc/esim.hip: the merge-path search of ev2h_esim_step_wide's merge passes, run on the host on host
  * arrays (the search is one __host__ __device__ function).  a [na] and b [nb] sorted ascending, 0 <= d <= na + nb: -> how many of the
  * first d keys of their merge come from a (an a key equal to a b key goes first); -1: a bad argument.  No device is touched. */
