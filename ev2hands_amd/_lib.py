@@ -103,6 +103,7 @@ W_EQUALIZED, W_UNEQUALIZED_OK = 1, 2
 # and for the fitting exports (ev2h_mano_joints_jacobian, ev2h_mano_fit, ev2h_mano_fit_opts_size, ev2h_mano_fit_seq,
 # ev2h_mano_fit_seq_opts_size, ev2h_mano_fit_seq_workspace_bytes), and for the event simulator
 # (ev2h_esim_scratch_bytes, ev2h_esim_step, ev2h_esim_scratch_bytes_wide, ev2h_esim_step_wide, ev2h_esim_compose, ev2h_esim_shade),
+# and for its forearms and jitter (ev2h_esim_jitter_rows, ev2h_esim_forearm_axes, ev2h_esim_forearms),
 # and for the pose track (ev2h_pose_track_prepare, ev2h_pose_track_rows,
 # ev2h_pose_track_hand_size).
 ABI_VERSION = 8     # 8: EV2H_PREC_F16 (one fp16 plane with f16x2's range machinery); 3: F16X2 range records; 4: ev2h_fp_mlp, ev2h_weights.fp1m; 5: window strides of the outputs; 6: ev2h_pack_weights, ev2h_weights.flags; 7: ev2h_sa_desc.xyz_out
@@ -134,6 +135,7 @@ class PoseTrackHand(C.Structure):
 POSE_TRACK_KEY, POSE_TRACK_COEF, POSE_TRACK_PARTS = 61, 14, 112      # EV2H_POSE_TRACK_*
 ESIM_MODES = {"frame": 0, "scaled": 1, "interpolated": 2}      # EV2H_ESIM_FRAME, _FRAME_SCALED, _INTERPOLATED
 ESIM_OVER_CAPACITY, ESIM_LOOP_BOUND, ESIM_OVER_SORT = 1, 2, 4     # the status bits of ev2h_esim_step's state[3]
+FOREARM_RECORD, FOREARM_LEFT, FOREARM_RIGHT = 12, -2, -3       # EV2H_FOREARM_*: floats per record, the face_id of a forearm pixel
 ESIM_SORT_MAX, ESIM_SORT_WIDE_MAX = 8192, 1 << 20               # max_events_per_frame of ev2h_esim_step and of ev2h_esim_step_wide
 FIT_GROUPS = ("global_orient", "hand_pose", "betas", "transl")      # bits 0..3 of ev2h_mano_fit_opts.free_mask
 
@@ -166,6 +168,7 @@ EXPORTS = [
     "ev2h_mano_fit_seq", "ev2h_mano_fit_seq_opts_size", "ev2h_mano_fit_seq_workspace_bytes",
     "ev2h_mano_fit_seq_segments", "ev2h_mano_fit_seq_segments_workspace_bytes",
     "ev2h_esim_scratch_bytes", "ev2h_esim_step", "ev2h_esim_scratch_bytes_wide", "ev2h_esim_step_wide", "ev2h_esim_compose", "ev2h_esim_shade",
+    "ev2h_esim_jitter_rows", "ev2h_esim_forearm_axes", "ev2h_esim_forearms",
     "ev2h_pose_track_prepare", "ev2h_pose_track_rows", "ev2h_pose_track_hand_size",
     # test hooks, not part of the stable interface (include/ev2hands_hip.h: "Test hooks"; ev2hands_amd/ops.py: *_rows16, dense_zsum, ...)
     "ev2h_dbg_fp_mlp_rows16", "ev2h_dbg_gemm_zsum_supported", "ev2h_dbg_gemm_zsum", "ev2h_dbg_attn_simfold_partials", "ev2h_dbg_attn_context_rows16",
@@ -298,6 +301,10 @@ def lib() -> C.CDLL:
     L.ev2h_dbg_esim_wide_sort.argtypes = [ci, ci, ci, ci, vp, ci, vp, C.c_double, ci, vp, ci, vp, C.c_size_t, vp]
     L.ev2h_esim_compose.argtypes = [vp, vp, vp, ci, ci, ci, ci, ci, ci, vp, vp]
     L.ev2h_esim_shade.argtypes = [vp, vp, vp, C.c_size_t, vp, ci, vp, ci, ci, ci, ci] + [C.c_float] * 9 + [vp, ci, ci, C.c_uint64, vp, vp, vp, ci, vp, vp]
+    L.ev2h_esim_jitter_rows.argtypes = [vp, vp, ci, ci, C.c_float, C.c_uint64, vp, vp, vp, vp]
+    fp = C.POINTER(C.c_float)                 # the small HOST arrays of ev2h_esim_forearm_axes
+    L.ev2h_esim_forearm_axes.argtypes = [vp, vp, vp, ci, fp, fp, fp, ci, C.c_float, C.c_float, C.POINTER(C.c_uint8), vp, vp]
+    L.ev2h_esim_forearms.argtypes = [vp, ci, ci, ci] + [C.c_float] * 4 + [ci] + [C.c_float] * 6 + [vp, ci, ci, vp, ci, vp, vp, vp, vp]
     L.ev2h_pose_track_hand_size.restype = C.c_size_t
     L.ev2h_pose_track_hand_size.argtypes = []
     L.ev2h_pose_track_prepare.argtypes = [vp, ci, vp, vp, vp, vp]

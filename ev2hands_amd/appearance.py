@@ -12,8 +12,9 @@ render pasted over the background wherever its grey level is above 10).
 The rule is the PROJECT'S OWN: include/ev2hands_hip.h (ev2h_esim_shade) and tests/ref_shade.py state it; pyrender's shader and its
 output encoding are not reproduced (the byte is the linear value, no transfer curve), parity unpinned.  lights="reference" restates
 generate_train_lights as a pure function of (seed, global frame) on Philox stream 5 (csrc/random.hpp): the project's own draws, made
-on the device from the simulator's own frame counter.  NOT provided: reading texture or background files, the forearm cylinders,
-generate_mesh's 5 mm per-frame jitter and augment_mano_sequence, shadows.
+on the device from the simulator's own frame counter.  The forearm cylinders and generate_mesh's 5 mm per-frame jitter are
+forearm.Forearms and EventSimulatorS(jitter_mm=...).  NOT provided: reading texture or background files (the caller's, by design)
+and shadows; augment_mano_sequence and clean_intersections are defined in the reference but never called there (dead code).
 """
 from __future__ import annotations
 
@@ -51,6 +52,8 @@ class HandAppearance:
             raise ValueError(f"HandAppearance: the hands' colour tables differ in size: {list(cl.shape)} and {list(cr.shape)}")
         self.nv = int(cl.shape[0])
         self.vertex_colors = torch.from_numpy(np.ascontiguousarray(np.concatenate([cl, cr], 0))).to(self.device)
+        # a hand's mean colour, rounded half up: what forearm.Forearms colours that hand's forearm with by default
+        self.mean_colors = {side: tuple(int(v) for v in np.floor(c.astype(np.float64).mean(0) + 0.5)) for side, c in (("left", cl), ("right", cr))}
         self.base_color_factor, self.metallic, self.roughness = float(base_color_factor), float(metallic), float(roughness)
         if not (0.0 <= self.base_color_factor <= 1.0 and 0.0 <= self.metallic <= 1.0 and 0.0 < self.roughness <= 1.0):
             raise ValueError("HandAppearance: base_color_factor and metallic in [0, 1], roughness in (0, 1] required")
@@ -74,6 +77,21 @@ class HandAppearance:
             # one row of padding: a table of no lights still has an address
             self.lights = torch.from_numpy(np.ascontiguousarray(np.concatenate([a, np.zeros((1, 6), dtype=np.float32)], 0))).to(self.device)
 
+    def light_source(self, F: int, lights, spare, drawn=None):
+        """-> (table, n_lights, per_frame) of a call over F frames: `lights` (float32 [F, L, 6] on the device) if given, else the
+        appearance's own table, else -- lights="reference" -- (None, 5, 0): `shade` then draws them into its light_table.  drawn: that
+        light_table once `shade` has filled it; the draw is then (drawn, 5, 1), which is what the forearm pass reads, so the two
+        launches of one call cannot disagree about the lights.  spare: any device tensor, the address a table of no lights gets."""
+        if lights is not None:
+            if not torch.is_tensor(lights) or lights.dim() != 3 or lights.shape[1] > MAX_LIGHTS:
+                raise ValueError(f"lights must be a float32 tensor [{F}, L <= {MAX_LIGHTS}, 6] on {self.device}")
+            n_lights = int(lights.shape[1])
+            _dev_tensor(lights, "lights", torch.float32, (F, n_lights, 6), self.device)
+            return (lights if n_lights else spare), n_lights, 1                 # no light: any address, nothing is read
+        if self.lights is None and drawn is not None:
+            return drawn, REFERENCE_LIGHTS, 1
+        return self.lights, self.n_lights, 0
+
     def shade(self, frames, depth, face_id, out, background=None, lights=None, frame_counter=None, light_table=None):
         """Shade what `frames` (a frames.DemoFrames) has just rendered: depth float32 / face_id int32 [F, H, W] as its `render` wrote them
         (the per-vertex records are still in its scratch) -> out uint8 [F, H, W, 3], returned.  background: uint8 [H, W, 3] on the
@@ -89,14 +107,8 @@ class HandAppearance:
         _dev_tensor(out, "out", torch.uint8, (F, H, W, 3), self.device)
         if background is not None:
             _dev_tensor(background, "background", torch.uint8, (H, W, 3), self.device)
-        table, n_lights, per_frame = self.lights, self.n_lights, 0
-        if lights is not None:
-            if not torch.is_tensor(lights) or lights.dim() != 3 or lights.shape[1] > MAX_LIGHTS:
-                raise ValueError(f"lights must be a float32 tensor [{F}, L <= {MAX_LIGHTS}, 6] on {self.device}")
-            n_lights, per_frame = int(lights.shape[1]), 1
-            _dev_tensor(lights, "lights", torch.float32, (F, n_lights, 6), self.device)
-            table = lights if n_lights else depth                               # no light: any address, nothing is read
-        elif table is None:
+        table, n_lights, per_frame = self.light_source(F, lights, depth)
+        if table is None:
             if frame_counter is None or light_table is None:
                 raise ValueError('lights="reference" needs frame_counter and light_table')
             if not torch.is_tensor(frame_counter) or frame_counter.dtype != torch.int64 or frame_counter.device != self.device or frame_counter.numel() < 1:

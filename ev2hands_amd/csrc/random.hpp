@@ -26,6 +26,11 @@
 //     per axis.  Every arithmetic step is one float32 rounding; the position is then mapped (x, y, z) -> (x, -y, -z) into the
 //     rasteriser's camera frame.  Blocks 1, 3, 5 and word 3 of blocks 7 and 9 are not used.  These are the project's own draws, not
 //     numpy's or Python's.
+//   stream 6, the translation jitter of a simulated frame's rendered hands (forearm.hip: jitter_rows_kernel; the reference's
+//     trans_jitter = 5 * np.random.random(3) / 1000, HandSimulator/twohands.py:67-73, as a pure function of (seed, global frame, hand)):
+//     window_id = the global frame number's low 32 bits, block = the hand (0 left, 1 right); words 0, 1, 2 give the uniforms of x, y, z
+//     as (word >> 8) * 2^-24; the jitter is (amplitude_mm * u) / 1000 metres, two float32 roundings, added to the float32 `transl` with
+//     one more.  Word 3 is not used.
 //   a 32-bit word u becomes an index below M by multiply-shift, (u * M) >> 32 in 64 bits.  There is NO rejection step, so the
 //   indices are not exactly uniform: some values are hit by ceil(2^32 / M) words and the others by floor(2^32 / M), a relative
 //   bias of at most M / 2^32 -- below 7.7e-6 for M <= 32768 (the largest table a window can have).
@@ -38,7 +43,7 @@ namespace ev2h_random {
 
 constexpr uint32_t PHILOX_M0 = 0xD2511F53u, PHILOX_M1 = 0xCD9E8D57u;        // round multipliers
 constexpr uint32_t PHILOX_W0 = 0x9E3779B9u, PHILOX_W1 = 0xBB67AE85u;        // key increments (Weyl sequence)
-constexpr uint32_t STREAM_SAMPLE = 0, STREAM_FPS = 1, STREAM_AUGMENT = 2, STREAM_FINETUNE = 3, STREAM_FLIP = 4, STREAM_LIGHTS = 5;
+constexpr uint32_t STREAM_SAMPLE = 0, STREAM_FPS = 1, STREAM_AUGMENT = 2, STREAM_FINETUNE = 3, STREAM_FLIP = 4, STREAM_LIGHTS = 5, STREAM_JITTER = 6;
 
 struct u32x4 { uint32_t v[4]; };
 

@@ -16,6 +16,7 @@
 #include "ev2hands_hip.h"
 #include "random.hpp"
 #include "render_layout.hpp"
+#include "shade_brdf.hpp"
 
 #include <math.h>
 
@@ -25,7 +26,6 @@ constexpr int SHD_MAX_LIGHTS = 8;
 constexpr int SHD_DRAW_LIGHTS = 5;            // generate_train_lights
 constexpr int SHD_MAX_FRAMES = 4096;          // esim.hip: ES_MAX_FRAMES, ES_MAX_PIXELS
 constexpr int SHD_MAX_PIXELS = 1 << 22;
-constexpr float SHD_PI = 3.14159265358979323846f;
 
 struct ShadeArgs {
     const int32_t* face_id;                   // [F][H][W]
@@ -67,7 +67,7 @@ __global__ __launch_bounds__(64) void shade_lights_kernel(uint64_t seed, const i
     o[3] = inten; o[4] = inten; o[5] = inten;
 }
 
-__device__ __forceinline__ uint8_t to_byte(float x) { return (uint8_t)(int)(fminf(fmaxf(x, 0.f), 1.f) * 255.f + 0.5f); }
+using ev2h_shade::to_byte;
 
 __global__ __launch_bounds__(RND_THREADS) void shade_kernel(ShadeArgs a, int tiles_x) {
     const int b = blockIdx.y, tid = threadIdx.x;
@@ -119,49 +119,8 @@ __global__ __launch_bounds__(RND_THREADS) void shade_kernel(ShadeArgs a, int til
             nx *= inv; ny *= inv; nz *= inv;
             const float z = a.depth[pix] / 1000.f;
             const float Px = (px - a.cx) * z / a.f, Py = (py - a.cy) * z / a.f, Pz = z;
-            const float plen = sqrtf(Px * Px + Py * Py + Pz * Pz);
-            const float vx = -Px / plen, vy = -Py / plen, vz = -Pz / plen;
-            float ndv = nx * vx + ny * vy + nz * vz;
-            if (ndv < 0.f) { nx = -nx; ny = -ny; nz = -nz; ndv = -ndv; }
-            float f0[3], cdiff[3];
-#pragma unroll
-            for (int k = 0; k < 3; ++k) {
-                f0[k] = 0.04f + (base[k] - 0.04f) * a.metallic;
-                cdiff[k] = base[k] * a.kd;
-            }
-            const float a2 = a.alpha2, oma2 = 1.f - a2;
             const float* lt = a.lights + (size_t)b * a.light_stride;             // uniform over the workgroup
-            for (int j = 0; j < a.n_lights; ++j) {
-                const float lx = lt[6 * j] - Px, ly = lt[6 * j + 1] - Py, lz = lt[6 * j + 2] - Pz;
-                const float d2 = lx * lx + ly * ly + lz * lz;
-                if (!(d2 > 0.f)) continue;
-                const float d = sqrtf(d2);
-                const float ux = lx / d, uy = ly / d, uz = lz / d;
-                const float ndl = nx * ux + ny * uy + nz * uz;
-                if (!(ndl > 0.f)) continue;
-                const float hx = ux + vx, hy = uy + vy, hz = uz + vz;
-                const float h2 = hx * hx + hy * hy + hz * hz;
-                if (!(h2 >= 1e-30f)) continue;
-                const float hl = sqrtf(h2);
-                const float hnx = hx / hl, hny = hy / hl, hnz = hz / hl;
-                const float vdh = vx * hnx + vy * hny + vz * hnz;
-                const float ndh = nx * hnx + ny * hny + nz * hnz;
-                const float m = fmaxf(0.f, 1.f - vdh);
-                const float m5 = m * m * m * m * m;
-                float spec = 0.f;                                                // D Vis
-                if (ndv > 0.f) {
-                    const float t = ndh * ndh * (a2 - 1.f) + 1.f;
-                    const float D = a2 / (SHD_PI * (t * t));
-                    const float vis = 0.5f / (ndl * sqrtf(ndv * ndv * oma2 + a2) + ndv * sqrtf(ndl * ndl * oma2 + a2));
-                    spec = D * vis;
-                }
-                const float geo = ndl / d2;
-#pragma unroll
-                for (int k = 0; k < 3; ++k) {
-                    const float Fr = f0[k] + (1.f - f0[k]) * m5;
-                    val[k] += ((1.f - Fr) * cdiff[k] / SHD_PI + Fr * spec) * (lt[6 * j + 3 + k] * geo);
-                }
-            }
+            ev2h_shade::add_lights(nx, ny, nz, Px, Py, Pz, base, a.metallic, a.alpha2, a.kd, lt, a.n_lights, val);
         }
     }
     if (!live) return;
@@ -169,7 +128,7 @@ __global__ __launch_bounds__(RND_THREADS) void shade_kernel(ShadeArgs a, int til
     if (covered) { o0 = to_byte(val[0]); o1 = to_byte(val[1]); o2 = to_byte(val[2]); }
     if (a.background) {
         bool keep = covered;
-        if (a.mask_rule) keep = ((1868 * (int)o0 + 9617 * (int)o1 + 4899 * (int)o2 + 8192) >> 14) > 10;       // an uncovered pixel is black: grey 0
+        if (a.mask_rule) keep = ev2h_shade::grey_keeps(o0, o1, o2);                  // an uncovered pixel is black: grey 0
         if (!keep) {
             const uint8_t* g = a.background + ((size_t)r * a.width + c) * 3;
             o0 = g[0]; o1 = g[1]; o2 = g[2];

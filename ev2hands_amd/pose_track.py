@@ -20,8 +20,10 @@ AAtoPCA states it; restated, summed in index order) and the camera transform (tr
 checked by its defining property: the layer's vertices and joints of the new rows are R * (those of the old rows) + t).  Where upstream
 rounds to float32 between the steps (torch.FloatTensor in transform_mano_params) this path stays in float64 and rounds each value once.
 
-NOT provided: the InterHand json and image readers, clean_intersections (trimesh booleans), augment_mano_sequence, the forearm meshes
-and the 5 mm per-frame jitter of generate_mesh.
+NOT provided: the InterHand json and image readers (files stay with the caller).  clean_intersections (trimesh booleans) and
+augment_mano_sequence are defined in the reference but never called there (dead code), so they are not restated.  The forearm meshes
+and the 5 mm per-frame jitter of generate_mesh belong to the render, not to the rows: forearm.Forearms and
+EventSimulatorS(jitter_mm=...); a Forearms built with the track's `camera` applies the reference's direction rule in the world frame.
 """
 from __future__ import annotations
 

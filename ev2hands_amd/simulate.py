@@ -18,13 +18,18 @@ What is the PROJECT'S OWN: timestamps="interpolated" is ESIM's rule (linear cros
 simulator's memory frame, stated in include/ev2hands_hip.h and tests/ref_esim.py; the reference's ColorESIM calls esim_torch, a CUDA
 extension that is not part of the reference tree, so parity with it is UNPINNED.  The frames `step` feeds the generator are DemoFrames'
 render (csrc/render.hip, itself unpinned against pyrender) coloured with one `hand_color` over a fixed `background`; with
+`forearms=` (forearm.Forearms) every present hand continues in the reference's forearm cylinder (csrc/forearm.hip; its pixels get face_id
+-2 / -3 and so label 0, as the reference's grey forearms do), and `jitter_mm=5` adds the reference's per-frame, per-hand translation jitter
+to the rendered mesh only (Philox stream 6; `annotation_table` keeps the caller's rows); with
 `appearance=` (appearance.HandAppearance) they are shaded instead by csrc/shade.hip: per-vertex colours, the reference's metallic-roughness
 material, ambient 0.1, five point lights drawn again for every frame (or a table of yours) and the reference's grey-level paste over
 `background` -- the project's own rule (tests/ref_shade.py), not pyrender's shader or its output encoding.  The labels are the render's own face_id (0 background, 1 left, 2 right), which is
 what the reference's segmentation render encodes.
 
-NOT provided: reading texture or background files (vertex colours and one background image are arguments), the forearm cylinders, the
-5 mm per-frame jitter of generate_mesh and augment_mano_sequence, shadows, the InterHand readers and .h5 / pickle writing.  The rows `step` takes are
+NOT provided: reading texture or background files (vertex colours and one background image are arguments), shadows, the InterHand
+readers and .h5 / pickle writing -- files stay with the caller by design.  augment_mano_sequence and clean_intersections are defined in
+the reference but never called there (dead code), so they are not restated.  One jitter draw per (frame, hand) serves the image and the
+labels here; the reference draws it independently for its colour and its segmentation render, which offsets them by up to 5 mm.  The rows `step` takes are
 camera-space, as camera_hand_info is; pose_track.PoseTrack makes them from keyframes (interpolation, AA -> PCA, camera transform).
 
 Every buffer is allocated in `begin`: `step_images` and `step` synchronise nothing, allocate nothing and read nothing back; `finish`
@@ -41,6 +46,7 @@ from . import _lib
 from ._lib import _dev_tensor
 from .events import OUTPUT_HEIGHT, OUTPUT_WIDTH, EventTableS
 from .appearance import REFERENCE_LIGHTS, HandAppearance
+from .forearm import Forearms
 from .frames import DemoFrames
 
 BACKGROUND_GREY = 159                      # color_event_simulator.py:151: the grey the reference's memory frame starts from
@@ -67,12 +73,25 @@ class EventSimulatorS:
     chunk = 64 and 32768; a full-sensor frame under the reference lights holds 12 300 events on average).
     background: uint8 [H, W, 3] (default all 159); hand_color: RGB.  f, cx, cy: the camera (DemoFrames' defaults).
     appearance: an appearance.HandAppearance -- `render` / `step` / `step_track` then shade the frames with it (hand_color is not used);
-    None: the flat colouring."""
+    None: the flat colouring.  forearms: a forearm.Forearms -- the forearm cylinders are drawn over every rendered chunk (lit with the
+    appearance, or flat in the hand's colour); None: none.  jitter_mm (>= 0, the reference: 5) and jitter_seed: uniform jitter in
+    [0, jitter_mm) per axis on the translation of the RENDERED hands, drawn per (seed, global frame, hand); 0: none, and the rows are
+    used as they are."""
 
     def __init__(self, device, hands, fps: float = 1000, threshold_pos: float = 0.4, threshold_neg: float = 0.4, eps: float = 1e-6,
                  timestamps: str = "interpolated", width: int = OUTPUT_WIDTH, height: int = OUTPUT_HEIGHT, capacity: int = 4_000_000,
                  chunk: int = 64, background=None, hand_color=(198, 134, 66), max_per_pixel: int = 64, max_events_per_frame: int = 8192,
-                 max_annotations: int = 65536, f: float | None = None, cx: float | None = None, cy: float | None = None, appearance=None):
+                 max_annotations: int = 65536, f: float | None = None, cx: float | None = None, cy: float | None = None, appearance=None,
+                 forearms=None, jitter_mm: float = 0.0, jitter_seed: int = 0):
+        self.jitter_mm, self.jitter_seed = float(jitter_mm), int(jitter_seed)
+        if not (np.isfinite(self.jitter_mm) and self.jitter_mm >= 0.0):
+            raise ValueError("jitter_mm must be a finite number >= 0")
+        if not 0 <= self.jitter_seed < 2 ** 64:
+            raise ValueError("jitter_seed must be an unsigned 64-bit integer")
+        if (forearms is not None or self.jitter_mm > 0) and hands is None:
+            raise ValueError("forearms and jitter_mm need the hands they follow (hands=None renders nothing)")
+        if forearms is not None and not isinstance(forearms, Forearms):
+            raise ValueError("forearms must be a forearm.Forearms")
         self.device = torch.zeros(0, device=device).device
         if self.device.type != "cuda":
             raise RuntimeError("EventSimulatorS runs on the GPU only (there is no CPU fallback)")
@@ -106,6 +125,11 @@ class EventSimulatorS:
                 raise ValueError("an appearance needs the hands it colours (hands=None renders nothing)")
             if not isinstance(appearance, HandAppearance) or appearance.device != self.device or appearance.nv != self.frames.nv:
                 raise ValueError(f"appearance must be a HandAppearance on {self.device} with {self.frames.nv} colours per hand")
+        self.forearms = forearms
+        if forearms is not None:
+            if forearms.device != self.device:
+                raise ValueError(f"forearms must be a Forearms on {self.device}")
+            forearms.resolved_colors(appearance, self.hand_color)               # raises here, not in the first step
         self.table = torch.from_numpy(log_table()).to(self.device)
         wide = self.mepf > _lib.ESIM_SORT_MAX                                   # up to 8192: the export and the scratch as they were
         self._step_name = "ev2h_esim_step_wide" if wide else "ev2h_esim_step"
@@ -134,8 +158,14 @@ class EventSimulatorS:
             self._joints = torch.empty(2, F, 21, 3, device=dev, dtype=torch.float32)
             self._frame = torch.empty(F, H, W, 3, device=dev, dtype=torch.uint8)
             self._face_id = torch.empty(F, H, W, device=dev, dtype=torch.int32)
-            if self.appearance is not None:                                     # what the shading reads and the lights it draws
+            if self.appearance is not None or self.forearms is not None:        # what the shading and the forearm pass read
                 self._depth = torch.empty(F, H, W, device=dev, dtype=torch.float32)
+            if self.forearms is not None:
+                self._records = torch.empty(F, 2, _lib.FOREARM_RECORD, device=dev, dtype=torch.float32)
+            if self.jitter_mm > 0:                                              # the rows the rendered hands take; the caller's stay as they are
+                P = 16 + self.hands["left"].ncomps
+                self._jittered = (torch.empty(F, P, device=dev, dtype=torch.float32), torch.empty(F, P, device=dev, dtype=torch.float32))
+            if self.appearance is not None:                                     # the lights it draws
                 self._light_table = torch.empty(F, REFERENCE_LIGHTS, 6, device=dev, dtype=torch.float32)
             self._track_rows = None                                             # what `step_track` has the track write
             if hasattr(self.hands["left"], "ncomps"):                           # (hands that hold faces only can render vertices, not rows)
@@ -180,7 +210,8 @@ class EventSimulatorS:
 
     def render(self, params_left, params_right, present=None, lights=None):
         """-> (rgb uint8 [F, H, W, 3], the render's frame, face_id): what `step` feeds the generator, views of buffers allocated in
-        `begin` that the next call overwrites.  lights (with an appearance only): float32 [F, L, 6] on the device, this call's lights
+        `begin` that the next call overwrites.  With forearms, face_id holds -2 / -3 on the pixels of the left / right forearm (the
+        render's frame does not show them); with jitter_mm the hands are rendered from jittered copies of the rows.  lights (with an appearance only): float32 [F, L, 6] on the device, this call's lights
         per frame in place of the appearance's."""
         self._begun()
         if self.frames is None:
@@ -193,9 +224,19 @@ class EventSimulatorS:
             raise ValueError("lights need an appearance (EventSimulatorS(appearance=...))")
         if present is not None:
             _dev_tensor(present, "present", torch.bool, (F, 2), self.device)
-        for h, (side, prm) in enumerate((("left", params_left), ("right", params_right))):
+        rows = [params_left, params_right]
+        for h, side in enumerate(("left", "right")):
+            _dev_tensor(rows[h], f"params_{side}", torch.float32, (F, 16 + self.hands[side].ncomps), self.device)
+        if self.jitter_mm > 0:
+            if rows[0].shape[1] != rows[1].shape[1]:
+                raise ValueError("jitter_mm needs rows of one width for both hands")
+            out = [t[:F] for t in self._jittered]
+            _lib.check(_lib.lib().ev2h_esim_jitter_rows(rows[0].data_ptr(), rows[1].data_ptr(), F, rows[0].shape[1], self.jitter_mm,
+                                                        self.jitter_seed, self.state.data_ptr(), out[0].data_ptr(), out[1].data_ptr(),
+                                                        _lib.stream_handle()), "ev2h_esim_jitter_rows")
+            rows = out
+        for h, (side, prm) in enumerate((("left", rows[0]), ("right", rows[1]))):
             hand = self.hands[side]
-            _dev_tensor(prm, f"params_{side}", torch.float32, (F, 16 + hand.ncomps), self.device)
             v = self._verts[h, :F]
             c = hand.consts()
             _lib.check(_lib.lib().ev2h_mano(C.byref(c), prm.data_ptr(), prm.shape[1], F, v.data_ptr(), 0, self._joints[h, :F].data_ptr(), 0,
@@ -208,11 +249,18 @@ class EventSimulatorS:
             frame, depth, face_id = self.frames.render(verts[0], verts[1], out=(self._frame[:F], self._depth[:F], self._face_id[:F]))
             self.appearance.shade(self.frames, depth, face_id, rgb, background=self.background, lights=lights, frame_counter=self.state,
                                   light_table=self._light_table)
+            if self.forearms is not None:
+                self.forearms.draw(self.frames, (self._joints[0, :F], self._joints[1, :F]), present, depth, face_id, rgb, self._records,
+                                   appearance=self.appearance, lights=lights, light_table=self._light_table, background=self.background)
             return rgb, frame, face_id
-        frame, _, face_id = self.frames.render(verts[0], verts[1], out=(self._frame[:F], None, self._face_id[:F]))
+        depth = self._depth[:F] if self.forearms is not None else None
+        frame, _, face_id = self.frames.render(verts[0], verts[1], out=(self._frame[:F], depth, self._face_id[:F]))
         r, g, b = self.hand_color
         _lib.check(_lib.lib().ev2h_esim_compose(frame.data_ptr(), face_id.data_ptr(), self.background.data_ptr(), F, self.w, self.h, r, g, b,
                                                 rgb.data_ptr(), _lib.stream_handle()), "ev2h_esim_compose")
+        if self.forearms is not None:
+            self.forearms.draw(self.frames, (self._joints[0, :F], self._joints[1, :F]), present, depth, face_id, rgb, self._records,
+                               hand_color=self.hand_color)
         return rgb, frame, face_id
 
     def step(self, params_left, params_right, present=None, lights=None) -> None:

@@ -1084,6 +1084,59 @@ int ev2h_esim_shade(const int32_t* face_id, const float* depth, const void* rend
                     float base_color_factor, float metallic, float roughness, float ambient_r, float ambient_g, float ambient_b,
                     const float* lights, int n_lights, int lights_per_frame, uint64_t seed, const int64_t* frame_counter,
                     float* light_table, const uint8_t* background, int mask_rule, uint8_t* rgb, ev2h_stream_t stream);
+/* The 5 mm jitter of the rendered hands (csrc/forearm.hip; the reference: HandSimulator/twohands.py:67-73, drawn again for every hand
+ * and frame, on the rendered mesh only -- the annotations keep the caller's rows).  rows_left / rows_right [n_frames][row_width]
+ * float32 (global_orient | hand_pose | betas | transl) are copied to out_left / out_right, which the caller owns; the three last
+ * columns get  transl + (amplitude_mm * u) / 1000  in float32, one rounding per operation, u = (word >> 8) * 2^-24 of words 0, 1, 2 of
+ * csrc/random.hpp stream 6 at (seed, window = *frame_counter + frame, block = hand: 0 left, 1 right).  frame_counter: a device int64
+ * (the simulator's state word EV2H_ESIM_STATE_FRAMES).  The caller's rows are never written; one lane per (frame, hand, axis);
+ * allocates nothing, does not synchronise.  EV2H_ERR_ARG before any launch: a null pointer, an output that is its input or the
+ * other output, n_frames outside 1 .. 4096, row_width outside 3 .. 4096, a negative or non-finite amplitude. */
+int ev2h_esim_jitter_rows(const float* rows_left, const float* rows_right, int n_frames, int row_width, float amplitude_mm,
+                          uint64_t seed, const int64_t* frame_counter, float* out_left, float* out_right, ev2h_stream_t stream);
+/* The forearm cylinders of the simulator's frames (csrc/forearm.hip; the reference: twohands.py:83-86 and manotosmplx.py:277-374, the
+ * convex hull of two 18-gon rings of radius 0.0275 m at the wrist and 1.8 m along `dir`).  The rule is the project's own: the capped
+ * cylinder the hull approximates is intersected analytically (the prism's sagitta is 0.42 mm; the reference's stray hull point
+ * root_opposite is dropped); tests/ref_forearm.py is its float64 statement, parity with the reference's meshes unpinned.
+ *
+ * ev2h_esim_forearm_axes: one record of EV2H_FOREARM_RECORD floats per (frame, hand) into records [n_frames][2][12], hand 0 = left:
+ *   (a[3], d[3], radius, length, colour[3], valid).  joints_* [n_frames][21][3] float32 metres as ev2h_mano writes them; a = joint 0
+ *   (the wrist), copied.  With R = rotation (row-major [9], null: identity), t = translation_mm / 1000 (null: 0), e = elbow_offset
+ *   [2][3] (left, right):  root_w = R^T (a - t);  d = normalise(R (root_w + e)) under reference_rule 1 (the reference's sum),
+ *   normalise(R (e - root_w)) under 0 (towards a fixed elbow); float32.  valid = 1 unless present [n_frames][2] (uint8, may be null)
+ *   is 0, the wrist is not finite or the direction's squared norm is zero or not finite: d is then 0 and the pass draws nothing
+ *   for that hand -- not an error.  rotation, translation_mm, elbow_offset and colors ([2][3] bytes, RGB) are HOST arrays read
+ *   during the call; every other pointer is device memory.
+ *
+ * ev2h_esim_forearms: the pass, after ev2h_render_hands and ev2h_esim_shade or ev2h_esim_compose on the same chunk, in place on
+ *   depth [n_frames][height][width] (mm), face_id and rgb [..][3].  Per pixel (r, c) the ray t (qx, qy, 1), qx = (c + 0.5 - cx) / f,
+ *   qy = (r + 0.5 - cy) / f, meets each valid cylinder (axis from a along d / |d|, radius, length, flat caps) in float64: both roots
+ *   of the side's quadratic with axial position in [0, length] and the two cap discs (a ray across which the quadratic's leading
+ *   coefficient is 0 is decided by the caps alone); the nearest of these with depth t * 1000 > znear is the cylinder's hit, so a
+ *   camera inside sees the inner wall.  The depth is rounded to float32; the nearer forearm is kept, an equal depth keeps the left.
+ *   The forearm owns the pixel when the render left no hand (depth == 0 or face_id < 0) or its depth is strictly less than the
+ *   hand's.  An owning lane writes depth, face_id = EV2H_FOREARM_LEFT / _RIGHT (negative: ev2h_esim_step labels them 0) and rgb;
+ *   every other pixel keeps its bytes.  lit 1: ev2h_esim_shade's value with the unit normal radial on the side and -d / +d on the
+ *   caps (turned towards the viewer), P from the float32 depth, albedo base_color_factor * colour / 255, the same material,
+ *   ambient and lights ([n_frames or 1][n_lights][6], lights_per_frame 1 or 0; after a drawn ev2h_esim_shade: its light_table, 5, 1);
+ *   over a background under mask_rule 1 a forearm pixel of grey level <= 10 shows the BACKGROUND's byte.  lit 0: the demo's
+ *   head-light I = min(1, 0.3 + 0.7 |n_z|), s = (float)(int)(I * 255 + 0.5) / 255, byte (uint8)(int)(s * colour + 0.5) per channel as
+ *   ev2h_esim_compose computes it; material, lights, background and mask_rule are not read.
+ *   One lane per pixel in the rasteriser's 16 x 16 tiles; a frame's records and lights are uniform over its workgroups; a wave
+ *   without a hit stops after the intersection; no atomics, every pixel is a function of its own frame.  Allocates nothing, does
+ *   not synchronise.  EV2H_ERR_ARG before any launch: a null pointer (background may be null; lights may be null at n_lights 0),
+ *   n_frames outside 1 .. 4096, width or height outside 1 .. 4096, width * height > 2^22, f <= 0, a non-finite camera, znear < 0,
+ *   lit or mask_rule outside 0 .. 1 and, under lit 1, everything ev2h_esim_shade lists for the material, ambient and lights. */
+#define EV2H_FOREARM_RECORD 12
+#define EV2H_FOREARM_LEFT (-2)
+#define EV2H_FOREARM_RIGHT (-3)
+int ev2h_esim_forearm_axes(const float* joints_left, const float* joints_right, const uint8_t* present, int n_frames,
+                           const float* rotation, const float* translation_mm, const float* elbow_offset, int reference_rule,
+                           float radius, float length, const uint8_t* colors, float* records, ev2h_stream_t stream);
+int ev2h_esim_forearms(const float* records, int n_frames, int width, int height, float f, float cx, float cy, float znear, int lit,
+                       float base_color_factor, float metallic, float roughness, float ambient_r, float ambient_g, float ambient_b,
+                       const float* lights, int n_lights, int lights_per_frame, const uint8_t* background, int mask_rule, float* depth,
+                       int32_t* face_id, uint8_t* rgb, ev2h_stream_t stream);
 
 /* ---- MANO keyframes -> the simulator's pose rows (csrc/pose_track.hip; HandSimulator/dataset/utils.py:11-113, interhand.py:69-158) ----
  * A hand's track is L keyframe rows keys [L][61] float64 = pose(48: 16 axis-angle joints) | shape(10) | trans(3) at the uniform knots
